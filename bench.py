@@ -14,11 +14,13 @@ running statistics are averaged, hgnn_amd.dp.LayerBucketAllReduce).
 Run:  python bench.py [--gpus N --steps K --warmup W]   (N > 1: starts the N ranks itself)
       python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
       (--gpus must equal the launcher's WORLD_SIZE)
-Prints ONE JSON line (rank 0) with the BASELINE metric, a live roofline of the
-dominant kernel class and HBM rooflines of the two aggregation classes (HIP
-events around their launches in a second and a third timed region of the same steps), a
-forward-only line (roofline_fwd), and the oracle's CPU time on a bounded sample
-with the parity check of the GPU step against it (rank 0, N=1 only).
+Prints ONE JSON line (rank 0) with the BASELINE metric.  A plain run sets up, settles and warms up,
+times the K steps and prints that line; --dump-outputs DIR also writes what the last timed step
+computed as DIR/<name>.npy.  With --full the line also carries the host / GPU attribution of a step,
+a live roofline of the dominant kernel class and HBM rooflines of the two aggregation classes
+(in-kernel stamps around their launches in a second and a third timed region of the same steps), a
+forward-only line (roofline_fwd), and the oracle's CPU time on a bounded sample with the parity
+check of the GPU step against it (rank 0, N=1 only); the run fails if that check does.
 """
 
 import argparse
@@ -79,19 +81,53 @@ def parse():
     ap.add_argument("--dp-single", type=int, default=0,
                     help="N > 1: one all-reduce of the whole gradient buffer after the backward instead of per-layer "
                          "buckets overlapped with it")
-    ap.add_argument("--attribution", type=int, default=1,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the attribution regions, the "
+                         "rooflines, the forward-only line and the CPU baseline with its parity check (each can "
+                         "still be switched by its own option below; without --full they default to off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (outputs, loss, input and "
+                         "parameter gradients; rank 0) as DIR/<name>.npy in float32")
+    ap.add_argument("--attribution", type=int, default=None,
                     help="host-enqueue and GPU-busy time per step, each over a region of its own")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=None)
     ap.add_argument("--cpu-bs", type=int, default=128,
                     help="graphs per step of the CPU baseline's timed protocol (bounded sample)")
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-steps", type=int, default=5)
-    ap.add_argument("--roofline", type=int, default=1)
-    ap.add_argument("--fwd-line", type=int, default=1, help="also time the forward alone (cfg2f)")
+    ap.add_argument("--roofline", type=int, default=None)
+    ap.add_argument("--fwd-line", type=int, default=None, help="also time the forward alone (cfg2f)")
     ap.add_argument("--graph", type=int, default=0,
                     help="capture the step (forward + backward) in a HIP graph and replay it (off by default: "
                          "the eager step is GPU-bound, DESIGN.md §8)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    for name in ("attribution", "cpu_baseline", "roofline", "fwd_line"):
+        if getattr(args, name) is None:
+            setattr(args, name, int(args.full))
+    return args
+
+
+DUMP_BUDGET = 60 << 20  # bytes of .npy payload a --dump-outputs directory may hold
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy (float32).  Past DUMP_BUDGET bytes in all, every array above
+    1 MiB keeps only a fixed, seeded sample of its flattened elements (the same indices in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: np.ascontiguousarray(v.detach().to(torch.float32).cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET:
+        small = sum(a.nbytes for a in host.values() if a.nbytes <= (1 << 20))
+        keep = max(0.0, (DUMP_BUDGET - small)) / (total - small)
+        rng = np.random.default_rng(0)
+        for k in sorted(host):
+            a = host[k]
+            if a.nbytes > (1 << 20):
+                idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * keep)), replace=False))
+                host[k] = a.reshape(-1)[idx]
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def make_batch(bs, seed, world=1, rank=0):
@@ -350,11 +386,15 @@ def main():
     # aggregation backward 19 -> 30 us per launch inside rocprofv3's own trace of a round-5 bench run)
     from hgnn_amd.net import TIMER_STAMPS
     wave_bound = 2 * (X.shape[0] * (X.shape[2] + XL.shape[2])) + 16384  # waves of the largest timed launch
+    # steps of every region after the `value` region (--full): --steps, but at most 50 -- a stamp timer holds
+    # 2 words per wave of every timed launch (0.8 GB per class at 50 steps of the default batch, and at most
+    # 2^31 words), and a long headline region needs no equally long attribution / roofline / forward regions
+    xsteps = max(1, min(args.steps, 50))
 
     def stamp_timer(k, steps_):
         n = max(1, per[k][1] // prof_steps * steps_ + 8)
         return KernelTimer(n, [k], mode=TIMER_STAMPS, stamp_words=2 * n * wave_bound)
-    timers = {k: stamp_timer(k, args.steps) for k in timed}
+    timers = {k: stamp_timer(k, xsteps) for k in timed}
     graph = None
     if args.graph:
         # The step (~90 kernel launches + Python autograd) is captured once and replayed; every
@@ -388,6 +428,12 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step holds after its last step: the model's outputs, the loss, the
+        # gradients of the inputs that require them and of every parameter (N > 1: after the all-reduce)
+        arrays = {"out": last_out[0], "loss": crit(last_out[0], T), "dX": X.grad, "dW": W.grad}
+        arrays.update({"grad." + k: p.grad for k, p in model.named_parameters()})
+        dump_outputs(args.dump_outputs, arrays)
     rank_ms = None
     comm = None
     if world > 1:
@@ -422,7 +468,7 @@ def main():
     if args.attribution and graph is None:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(xsteps):
             step()
         th = time.perf_counter() - t0
         torch.cuda.synchronize()
@@ -451,8 +497,8 @@ def main():
             span.append(iv[-1][1] - iv[0][0] if iv else 0.0)
         import statistics as _st
         attribution = {
-            "host_enqueue_ms_per_step": round(th * 1e3 / args.steps, 4),
-            "wall_ms_per_step": round(tw * 1e3 / args.steps, 4),
+            "host_enqueue_ms_per_step": round(th * 1e3 / xsteps, 4),
+            "wall_ms_per_step": round(tw * 1e3 / xsteps, 4),
             "gpu_busy_ms_per_step": round(_st.median(busy) / 1e3, 4) if busy else None,
             "gpu_span_ms_per_step": round(_st.median(span) / 1e3, 4) if span else None,
             "stamped_launches_per_step": per_step,
@@ -462,14 +508,14 @@ def main():
                      "all streams), gpu_span: first entry to last exit of the step's stamped launches"),
         }
 
-    # every timed class over its own region of args.steps eager steps, after the `value` region (event
+    # every timed class over its own region of xsteps eager steps, after the `value` region (event
     # records cost ~10 us each: 1.90 vs 1.72 ms per step measured on one box; events captured into a
     # HIP graph give no elapsed times either)
     timer_ms = {}
     for k in timed:
         torch.cuda.synchronize()
         with timers[k]:
-            for _ in range(args.steps):
+            for _ in range(xsteps):
                 step()
         torch.cuda.synchronize()
         timer_ms[k] = timers[k].elapsed(k)
@@ -485,19 +531,19 @@ def main():
     if timed:
         counts = RF.batch_counts(W.detach(), WL, Pm, Pd, Nb, Eb)
         ms, n = timer_ms[dominant]
-        roof = RF.roofline_entry(dominant, ms, n, counts, args.order, 5, args.d, args.layers, args.steps, pmc_path=pmc,
+        roof = RF.roofline_entry(dominant, ms, n, counts, args.order, 5, args.d, args.layers, xsteps, pmc_path=pmc,
                                  trace_path=ktr)
         roof["traffic_source"] = traffic_note
         if "frac_trace" in roof:
             roof["trace_source"] = trace_note
-        roof["timed_in"] = (f"a region of its own: {args.steps} eager steps, every wave of this class's launches "
+        roof["timed_in"] = (f"a region of its own: {xsteps} eager steps, every wave of this class's launches "
                             "stamping s_memrealtime at entry and exit (a launch = last exit - first entry; no "
                             "events in the stream); each aggregation class in another such region")
         roof["class_ms_per_step_profile"] = {RF.NAMES[k]: round(v[0] / prof_steps, 4) for k, v in per.items()}
         roof_hbm = {}
         for k in hbm_classes:
             kms, kn = timer_ms[k]
-            e = RF.roofline_entry(k, kms, kn, counts, args.order, 5, args.d, args.layers, args.steps, pmc_path=pmc,
+            e = RF.roofline_entry(k, kms, kn, counts, args.order, 5, args.d, args.layers, xsteps, pmc_path=pmc,
                                   trace_path=ktr)
             roof_hbm[RF.NAMES[k]] = {x: e[x] for x in (
                 "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
@@ -518,20 +564,20 @@ def main():
             fwd()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(xsteps):
             fwd()
         torch.cuda.synchronize()
-        fms = (time.perf_counter() - t0) * 1e3 / args.steps
-        nl = (args.layers * 2) * args.steps + 8  # aggregation launches of the forwards, with room
+        fms = (time.perf_counter() - t0) * 1e3 / xsteps
+        nl = (args.layers * 2) * xsteps + 8  # aggregation launches of the forwards, with room
         with KT(nl, [RF.K_AGG_FWD], mode=TIMER_STAMPS, stamp_words=2 * nl * wave_bound) as tf:
-            for _ in range(args.steps):
+            for _ in range(xsteps):
                 fwd()
             torch.cuda.synchronize()
             ams, an = tf.elapsed(RF.K_AGG_FWD)
         tf.close()
         counts_f = RF.batch_counts(W.detach(), WL, Pm, Pd, Nb, Eb)
         ffl, fby = RF.forward_work(counts_f, args.order, 5, args.d, args.layers)
-        agg = RF.roofline_entry(RF.K_AGG_FWD, ams, an, counts_f, args.order, 5, args.d, args.layers, args.steps)
+        agg = RF.roofline_entry(RF.K_AGG_FWD, ams, an, counts_f, args.order, 5, args.d, args.layers, xsteps)
         roof_fwd = {"workload": f"forward only (train-mode BN), {args.bs} graphs", "ms_per_forward": round(fms, 4),
                     "graphs_per_s": round(args.bs / fms * 1e3, 1),
                     "algorithmic_flops": ffl, "algorithmic_bytes": fby,

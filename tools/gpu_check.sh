@@ -3,24 +3,25 @@
 # first crash / timeout (exit codes other than pytest's 0/1).
 set -u
 cd "${GRAFT_REPO_ROOT:-.}"
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 STEPS=${STEPS:-20}
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
-  timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 240 --timeout-method thread ${PYTEST_ARGS:-} > gpurun_out/pytest_gpu.log 2>&1
+  timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 240 --timeout-method thread ${PYTEST_ARGS:-} > $OUT/pytest_gpu.log 2>&1
   rc=$?
-  echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log
+  echo "pytest rc=$rc"; tail -5 $OUT/pytest_gpu.log
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
-rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/smoke.log
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
+rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 600 python bench.py --steps $STEPS --warmup 5 ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
-rc=$?; echo "bench rc=$rc"; tail -3 gpurun_out/bench.log
+timeout -k 10 600 python bench.py --full --steps $STEPS --warmup 5 ${BENCH_ARGS:-} > $OUT/bench.log 2>&1
+rc=$?; echo "bench rc=$rc"; tail -3 $OUT/bench.log
 if [ $rc -ne 0 ]; then exit $rc; fi
 if [ "${PROFILE:-1}" = "1" ]; then
   export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run \
-      -- python3 bench.py --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 > gpurun_out/prof.log 2>&1
-  rc=$?; echo "rocprof rc=$rc"; tail -3 gpurun_out/prof.log
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run \
+      -- python3 bench.py --full --steps 10 --warmup 3 --cpu-baseline 0 --roofline 0 > $OUT/prof.log 2>&1
+  rc=$?; echo "rocprof rc=$rc"; tail -3 $OUT/prof.log
 fi
 exit 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch times of bench.py's roofline classes against a rocprofv3 kernel trace of the same command.
 
-usage: python tools/reconcile.py <run_kernel_trace.csv> <bench JSON line file>
+usage: python tools/reconcile.py <run_kernel_trace.csv> <bench JSON line file>   (of a `bench.py --full` run)
 For each class bench.py times (the dominant class and the two aggregation classes), prints the bench's
 avg_launch_us next to the trace's mean dispatch duration over every launch of the class's kernels in the
 whole run (hgnn_amd.roofline.CLASS_KERNELS), and their ratio.
