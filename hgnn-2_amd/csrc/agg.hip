@@ -447,11 +447,8 @@ static void agg_fwd_v(const AggFwdArgs& a0, dim3 g, hipStream_t s) {
     const bool v = (CG == 0 || vec_ok(CG, a.cg, a.xg, {})) && (CP == 0 || vec_ok(CP, a.cp, a.xp, {})) &&
                    (CG == 0 || vec_ok(CG, a.cg, a.out, {a.ldo, (long long)kk})) &&
                    (CP == 0 || vec_ok(CP, a.cp, a.out, {a.ldo, (long long)(JT - J0) * a.cg, (long long)a.cp}));
-    static const int rpw = [] {  // rows per wave: 1 (k_agg_fwd), 2 or 4 (k_agg_fwd_rpw; J_tot = 3 only)
-        const char* e = getenv("HGNN_AGG_RPW");
-        const int r = e ? atoi(e) : 2;
-        return r == 4 ? 4 : (r == 1 ? 1 : 2);
-    }();
+    // HGNN_AGG_RPW, rows per wave: 1 (k_agg_fwd), 2 or 4 (k_agg_fwd_rpw; J_tot = 3 only); 3 runs as 2
+    const int rpw = switches().agg_rpw == 3 ? 2 : switches().agg_rpw;
     if constexpr (JT == 3) {
         if (rpw > 1) {
             const dim3 g2(ceil_div(a.cap_rows, rpw * AGG_WV));

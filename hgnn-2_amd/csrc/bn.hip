@@ -933,25 +933,13 @@ static void bn2s_launch(const BnBwdArgs& a, hipStream_t s) {
     HGNN_KLAUNCH(k_bn_bwd_apply2s<L>, dim3(t2), dim3(256 * L), 0, s, a);
 }
 
-static bool bn2_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("HGNN_BN_BWD2");
-        return !e || e[0] != '0';
-    }();
-    return on;
-}
+static bool bn2_enabled() { return switches().bn_bwd2 != Tri::Off; }  // HGNN_BN_BWD2=0: at no width
 
 // The wide two-launch form (c = 64 / 128 / 256) is off by default since round 4: with the dW GEMM on bf16 MFMA
 // beside it, the three-launch form's 64-row tiles (many 256-thread blocks instead of ~91 of 1024 threads)
 // measured 1.254-1.265 vs 1.282-1.313 ms per step in five alternating pairs (config 2); HGNN_BN_BWD2=1
 // turns it back on
-static bool bn2_wide_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("HGNN_BN_BWD2");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
+static bool bn2_wide_enabled() { return switches().bn_bwd2 == Tri::On; }
 
 template <int L>
 static void bn2_launch(const BnBwdArgs& a, hipStream_t s) {
@@ -963,40 +951,43 @@ static void bn2_launch(const BnBwdArgs& a, hipStream_t s) {
     HGNN_KLAUNCH(k_bn_bwd_apply2<L>, dim3(t2), dim3(BN2_THREADS), 0, s, a);
 }
 
-int launch_bn_backward(const BnBwdArgs& a, hipStream_t s, int apply) {
-    const int tiles = bn_bwd_tiles(a.cap_rows);
-    // the paths without the atomic statistics still hand the next half a zeroed accumulator region
-    const bool acc_path =
-        a.acc64 && bn_vec4(a) && (a.ldy == 0 || a.ldy == a.c) && apply && a.c <= 1024 &&
-        !(bn2_enabled() && ceil_div(a.cap_rows, BN2_ROWS) <= 192 && (a.c == 4 || a.c == 8 || a.c == 16)) &&
-        !(bn2_wide_enabled() && ceil_div(a.cap_rows, BN2_ROWS) <= 192 && (a.c == 64 || a.c == 128 || a.c == 256));
-    if (a.acc64_zero && !acc_path)
-        HGNN_HOST_CHECK(hipMemsetAsync(a.acc64_zero, 0, (size_t)bn_acc_doubles(a.c) * sizeof(double), s));
-    if (a.ldy != 0 && a.ldy < a.c) return HGNN_ERR_ARG;
+// The launch sequences of the BN backward: part2s + apply2s (c = 4 / 8 / 16); part2 + apply2 (c = 64 / 128 / 256);
+// part4 -> apply4 on the atomic statistics (acc64), no k_bn_bwd_fin; part4 + fin (+ apply4); part + fin (+ apply).
+// bn_bwd_path is the one place that picks among them: the accumulator memset and the launches both follow it.
+enum class BnBwdPath { Narrow2s, Wide2, Part4Acc, Part4Fin, Scalar };
+static BnBwdPath bn_bwd_path(const BnBwdArgs& a, int apply, int tiles) {
     // a padded dY stride is written by the scalar apply only
-    const bool v4 = bn_vec4(a) && (a.ldy == 0 || a.ldy == a.c);
+    if (!bn_vec4(a) || !(a.ldy == 0 || a.ldy == a.c)) return BnBwdPath::Scalar;
     // (c / 4 a power of two: the per-wave shuffle reduction pairs the lanes of one channel group)
     // the two-launch forms sum every statistics partial in each apply block's prologue (O(tiles^2 C)
     // L2 reads): only up to 192 row tiles of capacity (49 K rows; config 2's edge half is 140 with 91
     // live); larger inputs take part4 + fin + apply4
-    const bool few = ceil_div(a.cap_rows, BN2_ROWS) <= 192;
-    if (apply && v4 && bn2_enabled() && few && tiles > 0 && (a.c == 4 || a.c == 8 || a.c == 16)) {
+    if (apply && tiles > 0 && ceil_div(a.cap_rows, BN2_ROWS) <= 192) {
+        if (bn2_enabled() && (a.c == 4 || a.c == 8 || a.c == 16)) return BnBwdPath::Narrow2s;
+        if (bn2_wide_enabled() && (a.c == 64 || a.c == 128 || a.c == 256)) return BnBwdPath::Wide2;
+    }
+    return a.acc64 && apply && a.c <= 1024 ? BnBwdPath::Part4Acc : BnBwdPath::Part4Fin;
+}
+
+int launch_bn_backward(const BnBwdArgs& a, hipStream_t s, int apply) {
+    const int tiles = bn_bwd_tiles(a.cap_rows);
+    const BnBwdPath path = bn_bwd_path(a, apply, tiles);
+    // Part4Acc's apply4 zeroes the next half's accumulator region itself; every other path hands it over zeroed here
+    if (a.acc64_zero && path != BnBwdPath::Part4Acc)
+        HGNN_HOST_CHECK(hipMemsetAsync(a.acc64_zero, 0, (size_t)bn_acc_doubles(a.c) * sizeof(double), s));
+    if (a.ldy != 0 && a.ldy < a.c) return HGNN_ERR_ARG;
+    if (path == BnBwdPath::Narrow2s || path == BnBwdPath::Wide2) {
         if (a.c == 4) bn2s_launch<1>(a, s);
         else if (a.c == 8) bn2s_launch<2>(a, s);
-        else bn2s_launch<4>(a, s);
-        HGNN_LAUNCH_CHECK();
-        return 0;
-    }
-    if (apply && v4 && tiles > 0 && bn2_wide_enabled() && few && (a.c == 64 || a.c == 128 || a.c == 256)) {
-        if (a.c == 64) bn2_launch<16>(a, s);
+        else if (a.c == 16) bn2s_launch<4>(a, s);
+        else if (a.c == 64) bn2_launch<16>(a, s);
         else if (a.c == 128) bn2_launch<32>(a, s);
         else bn2_launch<64>(a, s);
         HGNN_LAUNCH_CHECK();
         return 0;
     }
+    const bool v4 = path != BnBwdPath::Scalar, acc = path == BnBwdPath::Part4Acc;
     BnBwdArgs as = a;  // a stamp slot per launch (stamp-mode clock only)
-    // the atomic statistics (acc64): part4 -> apply4, no k_bn_bwd_fin
-    const bool acc = a.acc64 && v4 && apply && a.c <= 1024;
     if (!acc) {
         as.acc64 = nullptr;
         as.acc64_zero = nullptr;

@@ -16,7 +16,6 @@
 // gradients are summed per lane over a wave's nodes, then over lanes and waves (fp32), where the general
 // path sums per node and then over nodes in fp64.
 #include <cstdio>
-#include <cstdlib>
 
 #include "kernels.h"
 
@@ -735,7 +734,7 @@ int hgnn_ccn_small_forward(const hgnn_ccn_config* cfg, const float* d_X, const f
     const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, false);
     static bool attr = false;
     cs_lds_attr(&k_ccn1_small_fwd<CS_CF>, attr);
-    static const bool prof = getenv("HGNN_CCN_SMALL_PROF") != nullptr;
+    const bool prof = switches().ccn_small_prof;
     static unsigned long long* dprof = nullptr;
     if (prof) {
         if (!dprof) HGNN_HOST_CHECK(hipMalloc(&dprof, 32 * 8));

@@ -266,10 +266,7 @@ static void allow_lds(size_t lds) {
 // block per graph (512 at config 2) holds every SIMD's wave slots and blocks the main stream's BN-backward
 // statistics kernel until it ends (round-5 stamp timeline: 7-14 us of main-stream idle per node half).
 static int dwd_grid(int bs) {
-    static const int g = [] {
-        const char* e = getenv("HGNN_DWD_GRID");
-        return e ? atoi(e) : 256;
-    }();
+    const int g = switches().dwd_grid;
     return g <= 0 ? bs : std::min(bs, g);
 }
 
@@ -331,11 +328,7 @@ __global__ void __launch_bounds__(256) k_dw_dense_narrow(DwDenseArgs a) {
 }
 
 int launch_dw_dense(const DwDenseArgs& a, hipStream_t s) {
-    static const bool narrow_ok = [] {
-        const char* e = getenv("HGNN_DW_NARROW");
-        return !e || e[0] != '0';
-    }();
-    if (narrow_ok && a.f <= 16 && !a.dout) {
+    if (switches().dw_narrow && a.f <= 16 && !a.dout) {
         const size_t lds = sizeof(float) * (size_t)a.nmax * (a.jt * a.f + a.f);
         if (lds <= 64 * 1024) {
             const int gy = std::max(1, std::min(16, 512 / std::max(1, a.bs)));

@@ -11,8 +11,6 @@
 // per operand then feeds 4 consecutive MFMA steps.  Measured on the box
 // (the round-1 GEMM lab; tools/gemm4_lab.hip is the current one) against v2 on the config-2 shapes: node fwd 57 -> 30 us,
 // edge fwd 79 -> 51 us, edge dA 64 -> 48 us.
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "kernels.h"
@@ -704,21 +702,13 @@ __global__ void __launch_bounds__(64 * WGM * WGN) k_gemm5(const float* __restric
 // (dw3_kc): at config 2, 256 blocks (one per CU) measured 1.340 / 1.344 ms per step against 1.377 /
 // 1.378 for 512 and 1.401 / 1.404 for 1024 (same box, alternating runs) -- the dW kernel runs on the
 // side stream beside the main stream's backward, and more of its blocks crowd the main stream's
-// kernels off the CUs; HGNN_DW_BLOCKS overrides.
-static int dw3_target_blocks() {
-    static const int t = [] {
-        const char* e = getenv("HGNN_DW_BLOCKS");
-        const int v = e ? atoi(e) : 256;
-        return v >= 16 && v <= 4096 ? v : 256;
-    }();
-    return t;
-}
-
+// kernels off the CUs; HGNN_DW_BLOCKS (16..4096) overrides.
 int dw3_chunks(int r_cap, int o, int k) {
+    const Switches& sw = switches();
     const int tiles = ceil_div(o, 128) * ceil_div(k, 128);
     // 256 blocks at config 2 (5 output tiles); twice that for the wide networks (config 4, d = 128: 20
     // tiles, 3.39 -> 3.32 ms per step), whose main-stream kernels are long enough to leave room
-    const int target = getenv("HGNN_DW_BLOCKS") || tiles < 16 ? dw3_target_blocks() : 2 * dw3_target_blocks();
+    const int target = sw.dw_blocks_given || tiles < 16 ? sw.dw_blocks : 2 * sw.dw_blocks;
     int chunks = target / (tiles > 0 ? tiles : 1);
     // never more chunks than 64-row pieces of the capacity; a multiple of 8 (XCD-aware order),
     // rounded DOWN so the grid stays within the target: standalone on the config-2 edge dW shape
@@ -735,25 +725,13 @@ int dw3_chunks(int r_cap, int o, int k) {
 
 size_t dw3_slab_floats(int r_cap, int o, int k) { return (size_t)dw3_chunks(r_cap, o, k) * o * k; }
 
-bool dw_bf3_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("HGNN_DW_BF3");
-        return !e || e[0] != '0';
-    }();
-    return on;
-}
-
 // slabs[z][o][k] = sum_{r in chunk z} dY[r, o] A[r, k]
 int launch_gemm3_dw(const float* dy, int lddy, const float* a, int lda, const int* r_valid, int r_cap, int o, int k,
                     int nz, float* slabs, hipStream_t s, const DiagIdArgs* id) {
     if (r_cap <= 0) return 0;
     if (nz <= 0) return HGNN_ERR_ARG;
-    static const bool xcd = [] {
-        const char* e = getenv("HGNN_DW_XCD");
-        return !e || e[0] != '0';
-    }();
-    const bool bf3 = dw_bf3_enabled();
-    if (bf3) return launch_gemm_bf3_dw(dy, lddy, a, lda, r_valid, r_cap, o, k, nz, slabs, xcd, s, id);
+    const bool xcd = switches().dw_xcd;
+    if (dw_bf3_enabled()) return launch_gemm_bf3_dw(dy, lddy, a, lda, r_valid, r_cap, o, k, nz, slabs, xcd, s, id);
     if (id) return HGNN_ERR_UNSUPPORTED;  // the diagonal I / D columns: the split-bf16 kernel only
     HGNN_KLAUNCH((k_gemm3_tn<128, 128, 32, 4, 2>), dim3(ceil_div(o, 128), ceil_div(k, 128), nz), dim3(512), 0, s,
                        dy, lddy, a, lda, slabs, o, k, r_valid, nz, xcd && nz % 8 == 0 ? 1 : 0);
@@ -780,10 +758,7 @@ int launch_gemm3_fwd(const float* a, int lda, const int* m_valid, int m_cap, int
     // block tiles of 4 waves -- config 2's 9.7 K node rows make 608 blocks, 2-3 per CU, instead of
     // 304 64 x 64 blocks of 8 waves that left 48 CUs with two blocks and the rest with one (22.2 vs
     // 24.4 us per launch, same results bit for bit); HGNN_FWD_G5=1 the 64 x 64 tiles, 0 never, 2 always
-    static const int g5 = [] {
-        const char* e = getenv("HGNN_FWD_G5");
-        return e ? atoi(e) : 3;
-    }();
+    const int g5 = switches().fwd_g5;
     const long long waves32 = (long long)ceil_div(m_cap, 64) * ceil_div(n, 64) * 4;
     if (mfma16 && g5 > 0 && n % 64 == 0 && n <= 512 && (g5 == 2 || waves32 < 2 * 1024)) {
         const int gx = ceil_div(ceil_div(m_cap, 64), 8) * 8;
@@ -812,12 +787,8 @@ int launch_gemm3_fwd(const float* a, int lda, const int* m_valid, int m_cap, int
     p.bias = bias;
     p.relu_from = relu_from;
     p.bn_part = bn_part;
-    static const bool xcd = [] {
-        const char* e = getenv("HGNN_FWD_XCD");
-        return !e || e[0] != '0';
-    }();
     const int bn = n <= 128 ? 64 : 128;
-    p.xcd = xcd && ceil_div(n, bn) > 1;
+    p.xcd = switches().fwd_xcd && ceil_div(n, bn) > 1;
     const int gx = p.xcd ? ceil_div(ceil_div(m_cap, 64), 8) * 8 : ceil_div(m_cap, 64);  // padded tiles exit
     if (n <= 128) {
         // 64-column tiles up to 2d = 128: twice the blocks of 64 x 128 tiles, measured (round-1 GEMM lab)
@@ -836,16 +807,9 @@ int launch_gemm3_da(const float* dy, int lddy, const int* m_valid, int m_cap, in
     if (m_cap <= 0) return 0;
     if (o % 4 != 0) return HGNN_ERR_UNSUPPORTED;
     if ((long long)m_cap * lddy * 4 >= (1ll << 31) || (long long)kout * ldw * 4 >= (1ll << 31)) return HGNN_ERR_UNSUPPORTED;
-    static const bool dma = [] {
-        const char* e = getenv("HGNN_GEMM_DMA");
-        return !(e && e[0] == '0');
-    }();
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (dma && lddy % 4 == 0 && ldw % 4 == 0 && al(dy) && al(wt)) {
-        static const bool xcd = [] {
-            const char* e = getenv("HGNN_DA_XCD");
-            return !e || e[0] != '0';
-        }();
+    if (switches().gemm_dma && lddy % 4 == 0 && ldw % 4 == 0 && al(dy) && al(wt)) {
+        const bool xcd = switches().da_xcd;
         const int gx = xcd ? ceil_div(ceil_div(m_cap, 64), 8) * 8 : ceil_div(m_cap, 64);
         const dim3 g(gx, ceil_div(kout, 64));
         HGNN_KLAUNCH((k_gemm5<64, 64, 2, 2>), g, dim3(256), 0, s, dy, lddy, wt, ldw, m_valid, m_cap, kout, o, da, ldda,

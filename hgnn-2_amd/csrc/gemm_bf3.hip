@@ -624,11 +624,7 @@ int launch_gemm_bf3_dw(const float* dy, int lddy, const float* a, int lda, const
     // ring depth 4 (k_gemm_bf3_tn_ring<4>, round 5: 1.1038 vs 1.1146 ms median over eight alternating pairs against
     // the retired unringed form; depth 3 bimodal, depth 2 slower -- DESIGN.md §8 round 5)
     const dim3 g(ceil_div(o, 128), ceil_div(k, 128), nz);
-    static const int ring = [] {  // HGNN_DW_RING: 2..4 = k_gemm_bf3_tn_ring<depth>
-        const char* e = getenv("HGNN_DW_RING");
-        const int v = e ? atoi(e) : 4;
-        return v < 2 ? 2 : (v > 4 ? 4 : v);
-    }();
+    const int ring = switches().dw_ring;  // HGNN_DW_RING: 2..4 = k_gemm_bf3_tn_ring<depth>, default 4
     uint64_t* st = clock_stamps((long long)g.x * g.y * g.z * (D_NT / 64));
     const int xr = xcd && nz % 8 == 0 ? 1 : 0;
 #define HGNN_DW_RING_LAUNCH(D, I) \

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "switches.h"
 
 namespace hgnn {
 
@@ -328,11 +329,11 @@ int launch_gemm3_fwd(const float* a, int lda, const int* m_valid, int m_cap, int
                      int mfma16 = 0);
 int launch_gemm3_da(const float* dy, int lddy, const int* m_valid, int m_cap, int o, const float* wt, int ldw,
                     int kout, float* da, int ldda, hipStream_t s);
-// dW split-K: the host fixes the number of row chunks nz (a multiple of 8, ~dw3_target_blocks() blocks with
+// dW split-K: the host fixes the number of row chunks nz (a multiple of 8, ~HGNN_DW_BLOCKS blocks with
 // the output tiles); the kernels derive the chunk length from the device row count, so every chunk
 // holds rows whatever the batch's fill of its capacity
 int dw3_chunks(int r_cap, int o, int k);
-bool dw_bf3_enabled();  // the dW GEMM on split-bf16 MFMA (HGNN_DW_BF3 != 0)
+inline bool dw_bf3_enabled() { return switches().dw_bf3; }  // the dW GEMM on split-bf16 MFMA (HGNN_DW_BF3 != 0)
 __host__ __device__ inline int dw3_kc(int rows, int nz) {
     int kc = (rows + nz - 1) / nz;
     kc = (kc + 31) / 32 * 32;

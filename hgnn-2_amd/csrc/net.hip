@@ -10,7 +10,6 @@
 // activations live in one caller-provided workspace laid out here, so a
 // forward+backward is a fixed sequence of launches with no allocation and no
 // host synchronisation (graph-capturable).
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
@@ -97,19 +96,10 @@ bool valid_config(const hgnn_net_config* c) {
     return true;
 }
 
-static bool env_flag(const char* name, bool dflt) {
-    const char* e = getenv(name);
-    if (!e || !e[0]) return dflt;
-    return e[0] != '0';
-}
-
 // The forward Conv1d-pair GEMM on bf16 MFMA with three-way split operands (gemm_bf3.hip: fp32 accuracy,
 // 2.7x fewer MFMA cycles); HGNN_FWD_BF3=0: the fp32 MFMA kernels (launch_gemm3_fwd).  Line-graph networks
 // with 2d % 64 == 0 (the kernel's 64-column tiles).
-static bool fwd_bf3_c2(int c2) {
-    static const bool on = env_flag("HGNN_FWD_BF3", true);
-    return on && c2 % 64 == 0;
-}
+static bool fwd_bf3_c2(int c2) { return switches().fwd_bf3 && c2 % 64 == 0; }
 // Diagonal I / D columns (round 6; HGNN_DIAG_ID=1: on, off by default -- measured 1.110 vs 1.105 ms per step in three
 // of three alternating pairs at config 2: the aggregation lost 5 us per step, the forward and dW GEMMs' staging
 // gained 11 and 14): graph_operators' slices 0 and 1 are I and diag(D)
@@ -119,10 +109,7 @@ static bool fwd_bf3_c2(int c2) {
 // split-bf16 GEMMs build the I / D columns from the half's input x̂ as they stage it (DiagIdArgs), the same
 // values bit for bit.  For the halves whose G input is a BN'd layer output of 2d <= 256 channels (not the
 // raw inputs of layer 0), with the split-bf16 forward and dW GEMMs.
-static bool diag_id_on(int c2) {
-    static const bool on = env_flag("HGNN_DIAG_ID", false);
-    return on && fwd_bf3_c2(c2) && dw_bf3_enabled() && c2 <= 256;
-}
+static bool diag_id_on(int c2) { return switches().diag_id && fwd_bf3_c2(c2) && dw_bf3_enabled() && c2 <= 256; }
 
 Program build_program(const hgnn_net_config* c) {
     Program P;
@@ -551,8 +538,7 @@ static int side_stream(hipStream_t main_s, SideStream** out) {
         // dispatch acquire already order the data, and the fence's cache writeback / invalidate only delays
         // the main stream's next kernel -- 1.163-1.169 vs 1.193-1.197 ms per step in three alternating pairs
         // (profiles/r05_ab_event_fence.txt); HGNN_EVENT_FENCE=1 restores the fenced records
-        static const bool fence = env_flag("HGNN_EVENT_FENCE", false);
-        const unsigned ef = hipEventDisableTiming | (fence ? 0u : hipEventDisableSystemFence);
+        const unsigned ef = hipEventDisableTiming | (switches().event_fence ? 0u : hipEventDisableSystemFence);
         for (int i = 0; i < 2; ++i) HGNN_HOST_CHECK(hipEventCreateWithFlags(&ss.fork[i], ef));
         for (int i = 0; i < BWD_NBUF; ++i) HGNN_HOST_CHECK(hipEventCreateWithFlags(&ss.join[i], ef));
         // the end-of-backward join hands the side stream's final dW / bias gradients to the caller's stream,
@@ -570,17 +556,13 @@ static bool fwd_bf3(const Program& P) { return fwd_bf3_c2(P.c2); }
 // BN-backward statistics by fp64 atomics into accumulator copies, no k_bn_bwd_fin (round 6; HGNN_BN_ACC=0: the
 // per-tile partials and k_bn_bwd_fin).  The sums' order over the tiles is not fixed: the statistics can differ in the
 // last fp64 bits from run to run (a float flip of m1 / m2 once in ~1e9 values), where the fin path is bitwise
-// deterministic.
-static bool bn_acc_on() {
-    static const bool on = env_flag("HGNN_BN_ACC", true);
-    return on;
-}
+// deterministic.  The same switch puts the split-bf16 forward GEMM's BN sums on fp64 atomics (Half::bnf), so
+// with the defaults the forward BN statistics are not bitwise repeatable from run to run either; HGNN_BN_ACC=0
+// fixes both orders.
+static bool bn_acc_on() { return switches().bn_acc; }
 // the forward BN finalize in the forward GEMM's last block (FwdBnFin; HGNN_BN_FWD_FIN=0: k_bn_finalize): 1.093 vs
 // 1.106 ms median, five of five alternating pairs
-static bool bn_fwd_fin_on() {
-    static const bool on = env_flag("HGNN_BN_FWD_FIN", true);
-    return on;
-}
+static bool bn_fwd_fin_on() { return switches().bn_fwd_fin; }
 // The forward's first kernel zeroes both accumulator regions (k_plan; a CSR batch: the error word's memset)
 static void bn_acc_zero_meta(const Program& P, void* ws, BatchMeta& m) {
     if (!bn_acc_on()) return;
@@ -588,10 +570,7 @@ static void bn_acc_zero_meta(const Program& P, void* ws, BatchMeta& m) {
     m.zero64_n = (int)((P.acc_end - P.bnb_acc[0]) / sizeof(double));
 }
 // the dA GEMM on the split-bf16 kernel (k_gemm_bf3_fwd with a plain-store epilogue, B = WT's planes)
-static bool da_bf3(const Program& P) {
-    static const bool on = env_flag("HGNN_DA_BF3", true);
-    return on && P.c2p <= 128;
-}
+static bool da_bf3(const Program& P) { return switches().da_bf3 && P.c2p <= 128; }
 
 int net_forward(const hgnn_net_config* c, const hgnn_net_inputs* in, const hgnn_csr_batch* csr,
                 const float* const* prm, float* const* run, void* ws, float* out, hipStream_t s, Timer* tm) {
@@ -829,9 +808,9 @@ int net_backward(const hgnn_net_config* c, const hgnn_net_inputs* in, const hgnn
     SideStream* side = nullptr;
     // HGNN_SIDE=0: the weight-gradient work stays on the main stream, with no events at all (a
     // cross-stream event record / wait costs the main stream ~6-7 us of idle GPU per fork)
-    static const bool use_side = env_flag("HGNN_SIDE", true);
-    if (use_side) TRY(side_stream(s, &side));
-    static const bool serial_bwd = env_flag("HGNN_SERIAL_BWD", false);
+    if (switches().side) TRY(side_stream(s, &side));
+    // HGNN_SERIAL_BWD=1 (diagnostics): all on the main stream, so a kernel trace shows each kernel's own duration
+    const bool serial_bwd = switches().serial_bwd;
     // the readout's parameter gradients and its dense dW only feed gradients: on the side stream, forked
     // here, beside the main stream's readout aggregation backward and first halves
     hipStream_t rs = s;
@@ -852,7 +831,7 @@ int net_backward(const hgnn_net_config* c, const hgnn_net_inputs* in, const hgnn
     // HGNN_READOUT_ROW=0: the readout gradient materialised as a [rows][K] buffer and gathered.  The
     // readout-row kernels hold a graph's rows in LDS: configurations beyond it (wide 2d with a large
     // Nmax / Emax) take the materialised form as well.
-    static const bool ro_row = env_flag("HGNN_READOUT_ROW", true);
+    const bool ro_row = switches().readout_row;
     const bool lgr = needs_grad(P.last_gin), lpr = needs_grad(P.last_pin);
     ReadoutAggArgs ra{};
     ra.dout = dout;
@@ -945,7 +924,7 @@ int net_backward(const hgnn_net_config* c, const hgnn_net_inputs* in, const hgnn
     if (bn_acc_on() && P.halves.size() % 2 == 1)
         HGNN_HOST_CHECK(hipMemsetAsync(at<double>(ws, P.bnb_acc[0]), 0, (size_t)bn_acc_doubles(P.c2) * sizeof(double), s));
     // HGNN_BWD_TAIL=0: the round-4 tail (the last half forks after its dA GEMM, dX unpacked after the join)
-    static const bool bwd_tail = env_flag("HGNN_BWD_TAIL", true);
+    const bool bwd_tail = switches().bwd_tail;
     // The side stream also takes the dense operator gradient (W.requires_grad) of a node
     // half: it only accumulates into dW, so it leaves the dA -> aggregation-backward chain.
     // (Measured alternative, not kept: the gather half of the aggregation backward on a third
@@ -959,10 +938,7 @@ int net_backward(const hgnn_net_config* c, const hgnn_net_inputs* in, const hgnn
             HGNN_HOST_CHECK(hipStreamWaitEvent(side->s, side->fork[q & 1], 0));
         }
         hipStream_t main_s = s;
-        // HGNN_SERIAL_BWD=1 (diagnostics): everything on the main stream, so a kernel trace shows
-        // each kernel's standalone duration
-        static const bool serial = env_flag("HGNN_SERIAL_BWD", false);
-        if (side && !serial) s = side->s;  // TL records its timer events on the stream the kernel runs on
+        if (side && !serial_bwd) s = side->s;  // TL records its timer events on the stream the kernel runs on
         int r = 0;
         do {
             if (ndw_side) TL(HGNN_K_DW_DENSE, dw_dense(h.gin, dab, h.kp, false, 1));
@@ -1158,11 +1134,8 @@ struct ReplayCache {
 constexpr size_t REPLAY_MAX = 16;
 
 static bool replay_eligible(const hgnn_net_config* c) {
-    static const int mode = [] {
-        const char* v = getenv("HGNN_EXEC_GRAPH");
-        return !v ? -1 : (v[0] == '1' ? 1 : (v[0] == '0' ? 0 : -1));
-    }();
-    if (mode >= 0) return mode == 1;
+    const Tri mode = switches().exec_graph;  // HGNN_EXEC_GRAPH=0 / =1: never / always
+    if (mode != Tri::Auto) return mode == Tri::On;
     return (long long)c->bs * c->nmax <= 4096 && (c->kind == 0 || (long long)c->bs * c->emax <= 8192);
 }
 
@@ -1404,9 +1377,8 @@ void* hgnn_timer_create_ex(int max_launches, unsigned class_mask, int mode, long
 }
 
 void* hgnn_timer_create(int max_launches, unsigned class_mask) {
-    const char* e = getenv("HGNN_TIMER_MARKERS");
     return hgnn_timer_create_ex(max_launches, class_mask,
-                                e && e[0] == '1' ? HGNN_TIMER_MARKERS : HGNN_TIMER_DISPATCH, 0);
+                                hgnn::switches().timer_markers ? HGNN_TIMER_MARKERS : HGNN_TIMER_DISPATCH, 0);
 }
 
 void hgnn_timer_reset(void* timer) {

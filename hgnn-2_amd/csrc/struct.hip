@@ -12,8 +12,6 @@
 // compacts the nonzeros of each 64-column chunk.  The union of the J+2 slices
 // (or of Pm and Pd) is stored once per (row, col), so one gathered feature row
 // feeds every slice.
-#include <stdlib.h>
-
 #include "kernels.h"
 
 namespace hgnn {
@@ -824,22 +822,13 @@ static int extract_one(const ExtractArgs& a, dim3 grid, hipStream_t s) {
 }
 
 int launch_extract(const ExtractArgs& a, hipStream_t s) {
-    static const bool staged = [] {
-        const char* e = getenv("HGNN_EXTRACT_LDS");
-        return !(e && e[0] == '0');
-    }();
+    const Switches& sw = switches();
+    const bool staged = sw.extract_lds;  // HGNN_EXTRACT_LDS=0: the general kernel
     // HGNN_EXTRACT_REG=0: the LDS-staged kernel for the shapes the register-staged one takes
-    static const bool reg = [] {
-        const char* e = getenv("HGNN_EXTRACT_REG");
-        return !(e && e[0] == '0');
-    }();
-    if (staged && reg && a.kind0 == 0 && extract_reg_fits(a)) {
+    if (staged && sw.extract_reg && a.kind0 == 0 && extract_reg_fits(a)) {
         ExtractArgs as = a;
-        static const int dbg = [] {
-            const char* e = getenv("HGNN_XR_DBG");
-            return e ? atoi(e) : 0;
-        }();
-        // (diagnostics: a truncated launch ahead of the real one, which then runs as always)
+        const int dbg = sw.xr_dbg;
+        // (diagnostics, HGNN_XR_DBG: a truncated launch ahead of the real one, which then runs as always)
         for (int pass = dbg > 0 ? 0 : 1; pass < 2; ++pass) {
             as.dbg = pass == 0 ? dbg : 0;
             as.stamps = clock_stamps((long long)a.bs * XR_WAVES);
@@ -877,11 +866,7 @@ int launch_extract(const ExtractArgs& a, hipStream_t s) {
     const int kinds = a.dual ? X_SLOTS : 2;
     // HGNN_EXTRACT_SPLIT=1 (diagnostics): one launch per block slot, so a kernel trace times
     // each slot
-    static const bool split = [] {
-        const char* e = getenv("HGNN_EXTRACT_SPLIT");
-        return e && e[0] == '1';
-    }();
-    if (!split) return extract_one(a, dim3(a.bs, kinds), s);
+    if (!sw.extract_split) return extract_one(a, dim3(a.bs, kinds), s);
     for (int k = 0; k < kinds; ++k) {
         ExtractArgs b = a;
         b.kind0 = k;

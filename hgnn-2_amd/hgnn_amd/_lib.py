@@ -75,6 +75,8 @@ _L = ctypes.c_long
 SIGNATURES = {
     "hgnn_abi_version": ([], _I),
     "hgnn_status_string": ([_I], ctypes.c_char_p),
+    "hgnn_switch_name": ([_I], ctypes.c_char_p),
+    "hgnn_switch_value": ([ctypes.c_char_p, ctypes.POINTER(_I)], _I),
     "hgnn_net_param_count": ([ctypes.POINTER(NetConfig)], _I),
     "hgnn_net_bn_count": ([ctypes.POINTER(NetConfig)], _I),
     "hgnn_net_workspace_bytes": ([ctypes.POINTER(NetConfig)], ctypes.c_size_t),
@@ -155,6 +157,13 @@ def lib():
             fn.restype = res
         _lib = h
     return _lib
+
+
+def switch(name):
+    """The value of kernel switch HGNN_<name> as the library read it (csrc/switches.cpp, once per process)."""
+    v = ctypes.c_int()
+    check(lib().hgnn_switch_value(name.encode(), ctypes.byref(v)), f"hgnn_switch_value({name})")
+    return v.value
 
 
 def check(status, what):

@@ -9,6 +9,7 @@ written once (gather re-reads served on chip are not algorithmic traffic).
 
 import torch
 
+from ._lib import switch
 from .net import expected_k
 
 PEAK_HBM_GBS = 8000.0        # MI355X HBM3E spec (MI355X_MICROARCH.md)
@@ -53,11 +54,9 @@ def lg_halves(order, f_in, d, n_layers, jt):
 def diag_id(cg, cp, d):
     """Whether the executor builds a half's I / D operand columns in its GEMMs instead of aggregating them (net.hip
     diag_id_on: HGNN_DIAG_ID=1 (off by default), the split-bf16 forward and dW GEMMs, 2d % 64 == 0, 2d <= 256; halves whose G input
-    is a layer output of 2d channels)."""
-    import os
+    is a layer output of 2d channels).  The switches are the library's own reading of them (_lib.switch)."""
     c2 = 2 * d
-    on = (os.environ.get("HGNN_DIAG_ID", "0") == "1" and split_bf16(K_GEMM_FWD, d) and split_bf16(K_GEMM_DW, d)
-          and c2 <= 256)
+    on = bool(switch("HGNN_DIAG_ID")) and split_bf16(K_GEMM_FWD, d) and split_bf16(K_GEMM_DW, d) and c2 <= 256
     return on and cg == c2 and cp in (0, c2)
 
 
@@ -185,13 +184,12 @@ def _in_class(kcls, name):
 def split_bf16(kcls, d):
     """Whether the executor runs class kcls on the split-bf16 GEMMs at width d (net.hip fwd_bf3 / da_bf3,
     gemm3.hip launch_gemm3_dw; their switches HGNN_FWD_BF3 / HGNN_DA_BF3 / HGNN_DW_BF3)."""
-    import os
     if kcls == K_GEMM_FWD:
-        return (2 * d) % 64 == 0 and os.environ.get("HGNN_FWD_BF3", "1") != "0"
+        return (2 * d) % 64 == 0 and bool(switch("HGNN_FWD_BF3"))
     if kcls == K_GEMM_DA:
-        return (2 * d + 3) // 4 * 4 <= 128 and os.environ.get("HGNN_DA_BF3", "1") != "0"
+        return (2 * d + 3) // 4 * 4 <= 128 and bool(switch("HGNN_DA_BF3"))
     if kcls == K_GEMM_DW:
-        return os.environ.get("HGNN_DW_BF3", "1") != "0"
+        return bool(switch("HGNN_DW_BF3"))
     return False
 
 

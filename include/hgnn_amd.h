@@ -68,6 +68,12 @@ extern "C" {
 int hgnn_abi_version(void);
 const char* hgnn_status_string(int status);
 
+/* The HGNN_* kernel switches as the library read them from the environment, once, at its first use of any of
+ * them (INTEGRATION.md lists them).  Host-only, read-only: no GPU needed.  Flags report 0 / 1; the tri-state
+ * HGNN_EXEC_GRAPH and HGNN_BN_BWD2 report -1 (unset), 0 or 1; integer switches their value after range checking. */
+const char* hgnn_switch_name(int i);                 /* NULL past the last row */
+int hgnn_switch_value(const char* name, int* value); /* HGNN_OK, or HGNN_ERR_ARG for an unknown name */
+
 /* ------------------------------------------------------------------------
  * Network executor: GNN_lg.forward / GNN_simple.forward + autograd backward.
  *

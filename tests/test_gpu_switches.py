@@ -1,6 +1,6 @@
 """Every kept kernel alternate of the executor under a parity test (review r05 #9).
 
-The library reads its HGNN_* switches once per process (static initialisers), so each setting runs in a child
+The library reads its HGNN_* switches once per process (csrc/switches.cpp), so each setting runs in a child
 process (tests/switch_worker.py: GNN_lg order 2 at d = 64 and GNN_simple at d = 32, X and W requiring grad --
 widths where the split-bf16 GEMMs and the diagonal I / D columns are active), and every setting is checked
 against the fp64 oracle (oracle/ref_mnb.py) on SURVEY.md §8 c's bounds: outputs on the two-leg policy, every
@@ -37,7 +37,10 @@ GROUPS = {
               "HGNN_SERIAL_BWD": "1", "HGNN_DW_NARROW": "0", "HGNN_BN_ACC": "0"},
     "alt_b": {"HGNN_DW_RING": "3", "HGNN_AGG_RPW": "4", "HGNN_SIDE": "0", "HGNN_EXTRACT_REG": "0",
               "HGNN_EXTRACT_LDS": "0", "HGNN_BN_BWD2": "0", "HGNN_EXEC_GRAPH": "0", "HGNN_EXTRACT_SPLIT": "1",
-              "HGNN_BN_FWD_FIN": "0"},
+              "HGNN_BN_FWD_FIN": "0", "HGNN_DW_BLOCKS": "192"},
+    # the wide two-launch BN backward beside live fp64 accumulators (HGNN_BN_ACC at its default): every half
+    # hands the next one its accumulator region by memset (bn.hip launch_bn_backward)
+    "bn_bwd2_wide": {"HGNN_BN_BWD2": "1"},
 }
 
 
