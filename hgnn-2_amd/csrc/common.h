@@ -30,9 +30,16 @@
         if (_e != hipSuccess) return HGNN_ERR_HIP;                  \
     } while (0)
 
+// Return a library status (0: ok) to the caller unless it is ok
+#define TRY(x)                  \
+    do {                        \
+        int _r = (x);           \
+        if (_r) return _r;      \
+    } while (0)
+
 namespace hgnn {
 
-// Per-dispatch kernel clock (bench.py's per-class timer, net.hip Timer): while t_clock is set on the
+// Per-dispatch kernel clock (bench.py's per-class timer, timer.h Timer): while t_clock is set on the
 // enqueuing thread, HGNN_KLAUNCH launches through hipExtLaunchKernel with a start / stop event pair that
 // the runtime binds to the kernel's own dispatch (its begin / end timestamps, as rocprofv3's kernel trace
 // reports them) -- no marker packets between the kernels of the stream, so timing changes neither the

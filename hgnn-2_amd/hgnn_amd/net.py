@@ -1,7 +1,7 @@
 """Autograd binding of the network executor (hgnn_net_forward / _backward).
 
 One torch.autograd.Function runs a whole GNN_lg / GNN_simple forward as a
-single enqueue of HIP kernels (include/hgnn_amd.h, hgnn-2_amd/csrc/net.hip) and
+single enqueue of HIP kernels (include/hgnn_amd.h, hgnn-2_amd/csrc/net.hip over csrc/program.hip) and
 its backward as another, so `loss.backward()` in the reference's training
 loop (scripts/train_mnb.py:90) works unchanged.
 
@@ -232,7 +232,7 @@ class NetSpec:
 
 
 def expected_k(kind, order, f_in, d, n_layers, jt):
-    """Input widths (K) of every Conv1d, in ABI parameter order (mirrors net.hip build_program)."""
+    """Input widths (K) of every Conv1d, in ABI parameter order (mirrors program.hip build_program)."""
     ks = []
     c2 = 2 * d
     cn, ce = f_in, 1

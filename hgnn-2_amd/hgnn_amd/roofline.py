@@ -35,7 +35,7 @@ def batch_counts(W, WL, Pm, Pd, N_batch, E_batch):
 
 
 def lg_halves(order, f_in, d, n_layers, jt):
-    """(edge?, rows key, K, Cg, Cp) per half in program order, mirroring net.hip build_program."""
+    """(edge?, rows key, K, Cg, Cp) per half in program order, mirroring program.hip build_program."""
     ks, k_last = expected_k(1, order, f_in, d, n_layers, jt)
     out = []
     cn, ce = f_in, 1
@@ -52,7 +52,7 @@ def lg_halves(order, f_in, d, n_layers, jt):
 
 
 def diag_id(cg, cp, d):
-    """Whether the executor builds a half's I / D operand columns in its GEMMs instead of aggregating them (net.hip
+    """Whether the executor builds a half's I / D operand columns in its GEMMs instead of aggregating them (program.h
     diag_id_on: HGNN_DIAG_ID=1 (off by default), the split-bf16 forward and dW GEMMs, 2d % 64 == 0, 2d <= 256; halves whose G input
     is a layer output of 2d channels).  The switches are the library's own reading of them (_lib.switch)."""
     c2 = 2 * d
@@ -182,7 +182,7 @@ def _in_class(kcls, name):
 
 
 def split_bf16(kcls, d):
-    """Whether the executor runs class kcls on the split-bf16 GEMMs at width d (net.hip fwd_bf3 / da_bf3,
+    """Whether the executor runs class kcls on the split-bf16 GEMMs at width d (program.h fwd_bf3 / da_bf3,
     gemm3.hip launch_gemm3_dw; their switches HGNN_FWD_BF3 / HGNN_DA_BF3 / HGNN_DW_BF3)."""
     if kcls == K_GEMM_FWD:
         return (2 * d) % 64 == 0 and bool(switch("HGNN_FWD_BF3"))

@@ -1,4 +1,4 @@
-"""Replay of launch-bound executor calls (csrc/net.hip: a call met a third time with the same configuration
+"""Replay of launch-bound executor calls (csrc/replay.h: a call met a third time with the same configuration
 and device pointers is captured once into a HIP graph and replayed).  The replayed calls must give what the
 eager enqueue gives -- bit for bit, since the same kernels run on the same buffers -- and must read the
 buffers' current contents (inputs changed in place, parameters updated by an optimizer)."""
