@@ -10,7 +10,9 @@
 //   * runs every level (promotion + the two contractions + Linear + ReLU, utils_ccn.py:281-324) and the
 //     readout (model_ccn.py:50-64) -- forward: one dispatch,
 //   * backward: rebuilds the plan and the levels in LDS, then walks them back (one dispatch for one
-//     graph; a batch adds one reduction of the per-graph parameter partials).
+//     graph; a batch adds one reduction of the per-graph parameter partials),
+//   * training (k_ccn1_small_train): ONE workgroup runs the reference's whole per-graph loop -- forward, loss,
+//     backward, Adamax, then the next graph on the new weights -- in one dispatch.
 // Per level the arithmetic is the one-chunk path of k_ccn1_fwd / k_ccn1_bwd_node / k_ccn1_bwd_gather in
 // the same order, so forward values and input gradients are those of the general path; the weight
 // gradients are summed per lane over a wave's nodes, then over lanes and waves (fp32), where the general
@@ -357,12 +359,26 @@ __device__ __forceinline__ int cs_nodes(const CsArgs& a, int b, uint32_t& bad) {
     return n;
 }
 
+// Output o of the fc layer without its bias, in fp64 (k_ccn_readout's order): sum_k fcw[o][k] vec[k] over the
+// first 256 threads, then their 4 waves.  Valid in thread 0.
+__device__ __forceinline__ double cs_fc(const CsArgs& a, const CsLds& s, int o, int nf) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double acc = 0.0;
+    if (threadIdx.x < CS_RT)
+        for (int k = threadIdx.x; k < nf; k += CS_RT) acc += (double)a.fcw[o * nf + k] * (double)s.vec[k];
+    acc = wave_sum_d(acc);
+    __syncthreads();
+    if (lane == 0) s.dred[wv] = acc;
+    __syncthreads();
+    return s.dred[0] + s.dred[1] + s.dred[2] + s.dred[3];
+}
+
 template <int CF>
 __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const CsLds s = cs_carve(lds, a, false);
     CS_STAMP(0);
     if (threadIdx.x == 0) sbad = 0;
@@ -395,15 +411,8 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgs a) {
     for (int k = threadIdx.x; k < nf; k += CS_NT) a.feat[(long long)b * nf + k] = s.vec[k];
     // out = fc(feat) in fp64 (k_ccn_readout's order)
     for (int o = 0; o < a.n_out; ++o) {
-        double acc = 0.0;
-        if (threadIdx.x < CS_RT)
-            for (int k = threadIdx.x; k < nf; k += CS_RT) acc += (double)a.fcw[o * nf + k] * (double)s.vec[k];
-        acc = wave_sum_d(acc);
-        __syncthreads();
-        if (lane == 0) s.dred[wv] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            a.out[(long long)b * a.n_out + o] = (float)(s.dred[0] + s.dred[1] + s.dred[2] + s.dred[3] + (double)a.fcb[o]);
+        const double v = cs_fc(a, s, o, nf);
+        if (threadIdx.x == 0) a.out[(long long)b * a.n_out + o] = (float)(v + (double)a.fcb[o]);
     }
     CS_STAMP(30);
     bad = wave_or(bad);
@@ -415,7 +424,8 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgs a) {
 
 // One level of the backward walk (node pass, parameter gradients, gather), CF = this level's channel
 // bound (levels of hidden <= 2 take CF = 2: a quarter of the loads and selects of the 8-channel form).
-template <int CF, int CH>
+// DX = false (the training kernel, which needs no input gradient): level 0 ends after its parameter gradients.
+template <int CF, int CH, bool DX = true>
 __device__ void cs_bwd_level(const CsArgs& a, const CsLds& s, int b, int l, int n, int G, const float* Xg,
                              const float* dFc, float* dFn) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -495,6 +505,10 @@ __device__ void cs_bwd_level(const CsArgs& a, const CsLds& s, int b, int l, int 
             const int poff = l == 0 ? 0 : p0 + (l - 1) * p1;
             a.ppart[(long long)b * (p0 + (L - 1) * p1) + poff + p] = v;
         }
+    }
+    if (!DX && l == 0) {  // no dX wanted: the level-0 gather is skipped
+        __syncthreads();
+        return;
     }
     // gather: dF_{l-1}[j][u] = sum_{i in N(j)} [q valid] (drow_i[q] + dcol_i[pos of j]) + readout term;
     // level 0: dX[j] = the sum over u + d_j dsum  (k_ccn1_bwd_gather's order)
@@ -605,6 +619,182 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_bwd(CsArgs a) {
     for (int e = threadIdx.x; e < (a.nmax - n) * f; e += CS_NT) a.dX[((long long)b * a.nmax + n) * f + e] = 0.f;
 }
 
+// The per-graph training loop of scripts/train_ccn.py:31-73 in one dispatch: one workgroup runs forward, loss,
+// backward and the Adamax step of graph 0, then of graph 1, ... (per-graph SGD is sequential: graph g + 1 reads
+// the weights graph g wrote).  The pieces are the forward's and the backward's (cs_* above, the one-graph form:
+// CsArgs::bs = 1), k_mse_loss's loss and meters and k_adamax's element update (adamax_elem).
+constexpr int CS_TMAX = 2 * CS_LMAX + 2;    // parameter tensors: level weights and biases, fc weight and bias
+constexpr int CS_TRAIN_GMAX = 4096;         // graphs per dispatch
+constexpr int CS_OMAX = CS_NW * CS_PMAX;    // n_out bound: out / dout of the graph live in CsLds::red
+
+struct CsTrain {
+    const float* y;       // (G, n_out) raw targets
+    const float* clr;     // (G,) lr / (1 - beta1^t) of the dispatch's k-th applied step (a rejected graph takes none)
+    float t_mean, t_div;  // yn = (y - mean) / div, div = std + 1e-8
+    float w, beta2, eps, wd;  // w = 1 - beta1
+    // the parameters (mutable: CsArgs' W / B / fcw / fcb alias them; none of these is const __restrict__, so
+    // the re-staging of the next graph reads them by vector loads, after the fence) and the optimizer state
+    float* p[CS_TMAX];
+    float* m[CS_TMAX];
+    float* u[CS_TMAX];
+    float* stats;         // [4] loss, mae and their RunningAverages
+    int G;
+};
+
+// a word this block wrote earlier in the dispatch, read at a wave-uniform address: an agent-scope load keeps it
+// on the vector path (the scalar cache is not coherent with the block's own stores)
+__device__ __forceinline__ float cs_fresh(const float* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <int CF, int CH>
+__global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    __shared__ uint32_t sbad;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const CsLds s = cs_carve(lds, a, true);
+    const int h = a.h, f = a.f, L = a.L, nf = f + L * h, n_out = a.n_out;
+    const int nw = cs_woff(L, f, h), ntot = nw + n_out * nf + n_out;
+    const float* Xg = s.Xs;
+    float run_l = 0.f, run_m = 0.f;  // the RunningAverages (thread 0)
+    int applied = 0;                 // optimizer steps taken so far in this dispatch
+    if (threadIdx.x == 0) {
+        run_l = t.stats[2];
+        run_m = t.stats[3];
+    }
+    for (int g = 0; g < t.G; ++g) {
+        // 1. stage (the current weights) and plan
+        if (threadIdx.x == 0) sbad = 0;
+        uint32_t bad = 0;
+        const int n = cs_nodes(a, g, bad);
+        cs_stage(a, g, n, s, s.F);
+        bad |= cs_plan(n, s, s.F);
+        bad = wave_or(bad);
+        if (lane == 0 && bad) atomicOr(&sbad, bad);
+        const int G = s.off1[66];
+        const int rows = s.off1[n];
+        // 2. every level, kept; the readout sums; out = fc(feat)
+        for (int l = 0; l < L; ++l) {
+            const int cin = l == 0 ? f : h;
+            const float* fin = l == 0 ? nullptr : s.F + (size_t)(l - 1) * a.rcap * h;
+            float* fout = s.F + (size_t)l * a.rcap * h;
+            const float* Wl = s.Ws + cs_woff(l, f, h);
+            if (cin <= 2) cs_fwd_level<2>(s, n, G, Xg, fin, cin, Wl, h, fout);
+            else cs_fwd_level<CF>(s, n, G, Xg, fin, cin, Wl, h, fout);
+            __syncthreads();
+        }
+        cs_colsum<CF>(s, n, f, 0, [&](int r, int c) { return (double)s.deg[r] * (double)Xg[r * f + c]; });
+        for (int l = 0; l < L; ++l) {
+            const float* fl = s.F + (size_t)l * a.rcap * h;
+            cs_colsum<CF>(s, rows, h, f + l * h, [&](int r, int c) { return (double)fl[r * h + c]; });
+        }
+        // the readout features stay in vec for the fc gradient; out[g] is what the graph saw before its update
+        for (int o = 0; o < n_out; ++o) {
+            const double v = cs_fc(a, s, o, nf);
+            if (threadIdx.x == 0) {
+                const float ov = (float)(v + (double)cs_fresh(a.fcb + o));
+                a.out[(long long)g * n_out + o] = ov;
+                s.red[o] = ov;
+            }
+        }
+        __syncthreads();
+        const uint32_t gbad = sbad;
+        __syncthreads();
+        if (gbad) {  // a rejected graph: reported, no loss, no gradients, no step
+            if (threadIdx.x == 0) a.err[0] = a.tag * 256 + (int)gbad;  // vector store (host-mapped word)
+            continue;
+        }
+        // 3. loss, meters and dout (k_mse_loss's arithmetic on the normalised target); dout replaces out in red
+        double se = 0.0, ae = 0.0;
+        if (threadIdx.x < CS_RT)
+            for (int i = threadIdx.x; i < n_out; i += CS_RT) {
+                const float yn = (t.y[(long long)g * n_out + i] - t.t_mean) / t.t_div;
+                const float d = s.red[i] - yn;
+                se += (double)d * d;
+                ae += fabs((double)d);
+                s.red[i] = 2.0f * d / (float)n_out;
+            }
+        se = wave_sum_d(se);
+        ae = wave_sum_d(ae);
+        if (lane == 0) {
+            s.dred[wv] = se;
+            s.dred[CS_NW + wv] = ae;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double S = 0.0, A = 0.0;
+            for (int i = 0; i < CS_RT / 64; ++i) {
+                S += s.dred[i];
+                A += s.dred[CS_NW + i];
+            }
+            const float loss = (float)(S / n_out), mae = (float)(A / n_out);
+            run_l = run_l == 0.f ? loss : 0.9f * loss + 0.1f * run_l;
+            run_m = run_m == 0.f ? mae : 0.9f * mae + 0.1f * run_m;
+            t.stats[0] = loss;
+            t.stats[1] = mae;
+            t.stats[2] = run_l;
+            t.stats[3] = run_m;
+        }
+        // 4. backward, k_ccn1_small_bwd's one-graph form: fc gradients from dout and feat, dsum, the levels
+        const float* dob = s.red;
+        for (int w = threadIdx.x; w < n_out * nf + n_out; w += CS_NT) {
+            if (w < n_out * nf) a.gfcw[w] = (float)((double)dob[w / nf] * (double)s.vec[w % nf]);
+            else a.gfcb[w - n_out * nf] = (float)(double)dob[w - n_out * nf];
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < nf; k += CS_NT) {
+            float v = 0.f;
+            for (int o = 0; o < n_out; ++o) v = fmaf(dob[o], a.fcw[o * nf + k], v);
+            s.vec[k] = v;
+        }
+        __syncthreads();
+        float* dFc = s.dF0;
+        float* dFn = s.dF1;
+        for (int l = L - 1; l >= 0; --l) {
+            if ((l == 0 ? f : h) <= 2) cs_bwd_level<2, CH, false>(a, s, g, l, n, G, Xg, dFc, dFn);
+            else cs_bwd_level<CF, CH, false>(a, s, g, l, n, G, Xg, dFc, dFn);
+            float* x = dFc;
+            dFc = dFn;
+            dFn = x;
+        }
+        // 5. Adamax over every parameter element (flat: the levels in Ws' order, then fc weight and bias), on the
+        // gradients other threads have just written
+        __threadfence();
+        __syncthreads();
+        const float clr = t.clr[applied++];
+        for (int e = threadIdx.x; e < ntot; e += CS_NT) {
+            int ti, q;
+            const float* gp;
+            if (e < nw) {
+                int l = 0;
+                while (l + 1 < L && e >= cs_woff(l + 1, f, h)) ++l;
+                q = e - cs_woff(l, f, h);
+                const int hk = h * 2 * (l == 0 ? f : h);
+                const bool isw = q < hk;
+                ti = 2 * l + (isw ? 0 : 1);
+                gp = isw ? a.gW[l] : a.gB[l];
+                q = isw ? q : q - hk;
+            } else if (e < nw + n_out * nf) {
+                ti = 2 * L;
+                gp = a.gfcw;
+                q = e - nw;
+            } else {
+                ti = 2 * L + 1;
+                gp = a.gfcb;
+                q = e - nw - n_out * nf;
+            }
+            float p = t.p[ti][q], m = t.m[ti][q], u = t.u[ti][q];
+            adamax_elem(p, gp[q], m, u, clr, t.w, t.beta2, t.eps, t.wd);
+            t.m[ti][q] = m;
+            t.u[ti][q] = u;
+            t.p[ti][q] = p;
+        }
+        // 6. the new weights visible to the next graph's staging
+        __threadfence();
+        __syncthreads();
+    }
+}
+
 // Batches: parameter gradient = sum over graphs in fp64, one wave per entry (the level entries, then fc
 // weight and bias from dout and the readout features, k_ccn_readout_bwd's order).
 __global__ void __launch_bounds__(256) k_ccn1_small_reduce(CsArgs a) {
@@ -669,7 +859,7 @@ CsArgs cs_args(const hgnn_ccn_config* c, const float* X, const float* adj, const
     a.fcb = params[2 * c->layers + 1];
     const int nf = c->f_in + c->layers * c->hidden;
     a.feat = static_cast<float*>(ws);
-    a.ppart = reinterpret_cast<float*>(static_cast<char*>(ws) + (4 * (size_t)c->bs * nf + 255) / 256 * 256);
+    if (ws) a.ppart = reinterpret_cast<float*>(static_cast<char*>(ws) + (4 * (size_t)c->bs * nf + 255) / 256 * 256);
     return a;
 }
 
@@ -791,6 +981,68 @@ int hgnn_ccn_small_backward(const hgnn_ccn_config* cfg, const float* d_X, const 
         HGNN_KLAUNCH(k_ccn1_small_reduce, dim3((outs + 3) / 4), dim3(256), 0, s, a);
         HGNN_LAUNCH_CHECK();
     }
+    return HGNN_OK;
+}
+
+int hgnn_ccn_small_train_supported(const hgnn_ccn_config* cfg) {
+    if (!cfg) return 0;
+    hgnn_ccn_config one = *cfg;  // a property of the model and nmax: the dispatch walks its graphs one at a time
+    one.bs = 1;
+    return cs_ok(&one) && one.n_out <= CS_OMAX ? 1 : 0;
+}
+
+int hgnn_ccn_small_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
+                         const float* d_y, double t_mean, double t_std, float* const* params, float* const* grads,
+                         float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
+                         double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
+                         int32_t* d_err, int32_t tag, void* stream) {
+    if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
+    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || !exp_inf || !d_clr || !d_stats || !d_out ||
+        !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > CS_TRAIN_GMAX)
+        return HGNN_ERR_ARG;
+    const int nt = 2 * cfg->layers + 2;
+    for (int k = 0; k < nt; ++k)
+        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_inf[k]) return HGNN_ERR_ARG;
+    CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, nullptr);
+    a.bs = 1;  // the one-graph form of the backward: gradients written directly; the kernel passes b = g
+    a.out = d_out;
+    a.err = d_err;
+    a.tag = tag;
+    for (int l = 0; l < cfg->layers; ++l) {
+        a.gW[l] = grads[2 * l];
+        a.gB[l] = grads[2 * l + 1];
+    }
+    a.gfcw = grads[2 * cfg->layers];
+    a.gfcb = grads[2 * cfg->layers + 1];
+    CsTrain t{};
+    t.y = d_y;
+    t.clr = d_clr;
+    // scalars combine in double and reach the kernel as fp32, as the reference's Python floats reach torch
+    t.t_mean = (float)t_mean;
+    t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
+    t.w = (float)(1.0 - beta1);
+    t.beta2 = (float)beta2;
+    t.eps = (float)eps;
+    t.wd = (float)weight_decay;
+    for (int k = 0; k < nt; ++k) {
+        t.p[k] = params[k];
+        t.m[k] = exp_avg[k];
+        t.u[k] = exp_inf[k];
+    }
+    t.stats = d_stats;
+    t.G = cfg->bs;
+    const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, true);
+    hipStream_t s = (hipStream_t)stream;
+    if (cfg->hidden <= 2) {
+        static bool attr = false;
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2>), dim3(1), dim3(CS_NT), lds, s, a, t);
+    } else {
+        static bool attr = false;
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF>), dim3(1), dim3(CS_NT), lds, s, a, t);
+    }
+    HGNN_LAUNCH_CHECK();
     return HGNN_OK;
 }
 

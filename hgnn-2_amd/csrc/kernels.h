@@ -502,6 +502,19 @@ bool readout_row_fits(const ReadoutAggArgs& ra, const DwDenseArgs* dw);
 // dW of the readout layer's graph_oper: dW[b, n, m, j] (+)= sum_f R_b[j F + f] X[m, f], every n
 int launch_dw_readout(const DwDenseArgs& a, hipStream_t s);
 
+// ---------------------------------------------------------------- optimizer
+// One element of torch.optim.Adamax in torch's operation order (train.hip): g += wd p; m = lerp(m, g, w) with
+// w = 1 - beta1 < 0.5; u = max(beta2 u, |g| + eps); p -= lr_c m / u with lr_c = lr / (1 - beta1^t).  The one
+// definition of the update: k_adamax and the CCN training kernel (ccn_small.hip) both inline it.
+__device__ __forceinline__ void adamax_elem(float& p, float g, float& m, float& u, float lr_c, float w, float beta2,
+                                            float eps, float wd) {
+    if (wd != 0.f) g = g + wd * p;
+    const float m0 = m;
+    m = m0 + w * (g - m0);  // torch lerp, weight < 0.5
+    u = fmaxf(u * beta2, fabsf(g) + eps);
+    p = p + (-lr_c) * (m / u);  // addcdiv_(m, u, value = -clr)
+}
+
 // CCN-2D one-workgroup-per-graph path (ccn2_small.hip) behind hgnn_ccn_small_* for order 2
 bool ccn2_small_ok(const hgnn_ccn_config* c);
 size_t ccn2_small_workspace_bytes(const hgnn_ccn_config* c);

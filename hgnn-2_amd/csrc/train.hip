@@ -117,15 +117,45 @@ __global__ void __launch_bounds__(256) k_adamax(AdamaxTable tab, float lr_c, flo
     while (t + 1 < tab.count && (int)blockIdx.x >= tab.start[t + 1]) ++t;
     const int i = ((int)blockIdx.x - tab.start[t]) * 256 + threadIdx.x;
     if (i >= tab.n[t]) return;
-    float g = tab.g[t][i];
-    const float p = tab.p[t][i];
-    if (wd != 0.f) g = g + wd * p;
-    const float m0 = tab.m[t][i];
-    const float m = m0 + w * (g - m0);  // torch lerp, weight < 0.5
-    const float u = fmaxf(tab.u[t][i] * beta2, fabsf(g) + eps);
+    float p = tab.p[t][i], m = tab.m[t][i], u = tab.u[t][i];
+    adamax_elem(p, tab.g[t][i], m, u, lr_c, w, beta2, eps, wd);
     tab.m[t][i] = m;
     tab.u[t][i] = u;
-    tab.p[t][i] = p + (-lr_c) * (m / u);  // addcdiv_(m, u, value = -clr)
+    tab.p[t][i] = p;
+}
+
+// Evaluation meters of scripts/test_ccn.py:34-67 over G graphs' outputs: [mean_g MSE_g, mean_g MAE_g] with the
+// target normalised as in the training kernel (true division by the fp32 divisor).  One block; fp64 sums in a
+// fixed order (graphs strided over the threads, lanes, then the waves in order): the same bits every call.
+__global__ void __launch_bounds__(256) k_ccn_eval_loss(const float* __restrict__ out, const float* __restrict__ y,
+                                                       int G, int n_out, float t_mean, float t_div,
+                                                       float* __restrict__ res) {
+    __shared__ double red[2][4];
+    double se = 0.0, ae = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) {
+        double s = 0.0, a = 0.0;
+        for (int o = 0; o < n_out; ++o) {
+            const float yn = (y[(long long)g * n_out + o] - t_mean) / t_div;
+            const float d = out[(long long)g * n_out + o] - yn;
+            s += (double)d * d;
+            a += fabs((double)d);
+        }
+        se += s / n_out;
+        ae += a / n_out;
+    }
+    se = wave_sum_d(se);
+    ae = wave_sum_d(ae);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = se;
+        red[1][threadIdx.x >> 6] = ae;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double S = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        const double A = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        res[0] = G > 0 ? (float)(S / G) : 0.f;
+        res[1] = G > 0 ? (float)(A / G) : 0.f;
+    }
 }
 
 }  // namespace
@@ -149,6 +179,16 @@ int hgnn_xent_loss(const float* d_out, const float* d_t, int n, int c, float* d_
     if (!d_out || !d_t || !d_stats || !d_err || n < 0 || c < 1) return HGNN_ERR_ARG;
     HGNN_KLAUNCH(k_xent_loss, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_t, n, c,
                        d_stats, d_dout, d_err);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+int hgnn_ccn_eval_loss(const float* d_out, const float* d_y, int n_graphs, int n_out, double t_mean, double t_std,
+                       float* d_res, void* stream) {
+    if (!d_out || !d_y || !d_res || n_graphs < 0 || n_out < 1) return HGNN_ERR_ARG;
+    const float div = (float)(t_std + 1e-8);  // std + 10 ** -8 in double, then fp32 (test_ccn.py:43)
+    HGNN_KLAUNCH(k_ccn_eval_loss, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_y, n_graphs,
+                       n_out, (float)t_mean, div, d_res);
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
 }

@@ -157,3 +157,228 @@ class TrainStep:
         if int(self._err.item()):
             self._err.zero_()
             raise RuntimeError("hgnn_amd: class target outside [0, dim_output) or not an integer")
+
+
+CCN_TRAIN_MAX_GRAPHS = 4096  # csrc/ccn_small.hip CS_TRAIN_GMAX: graphs per hgnn_ccn_small_train dispatch
+
+
+class CcnTrainStep:
+    """The per-graph training loop of scripts/train_ccn.py:31-73 for a CCN_1D / CCN_2D drop-in model, and
+    the evaluation loop of scripts/test_ccn.py:23-67, without host round trips.
+
+    The reference runs, per graph: the normalised target, net(X, A + I), the MAE and MSE meters (.item()
+    twice), backward and one Adamax step.  step(X, adj, n_batch, y) runs exactly that sequence over the
+    graphs of a padded batch in index order -- graph g + 1 sees the weights graph g left:
+
+      fused    hgnn_ccn_small_train: one dispatch for the whole list (CCN_1D within the small-graph bounds:
+               graphs of <= 64 nodes, input_feats and hidden_size <= 8)
+      unfused  per graph forward_batch on the one-graph slice, hgnn_mse_loss, autograd backward and
+               hgnn_adamax_step: the same arithmetic from the separate entry points (CCN_2D, larger graphs,
+               wider channels)
+
+    fused=None takes the fused kernel wherever hgnn_ccn_small_train_supported allows it, fused=False never,
+    fused=True raises where it is not supported.  Neither path synchronises with the host.
+
+    A graph the fused kernel rejects (missing self loop, asymmetric pattern, n_b outside [0, nmax]) takes no
+    step and updates no meter; the error shows at the next check (hgnn_amd.net.check_errors(), or at once
+    under HGNN_STRICT=1).  step_count still counts it, so later step sizes then differ from a run without it.
+
+    Only the regression branch (mean != 0) is built: the reference's `mean == 0` class-target branch
+    (train_ccn.py:39-41, 56-57) raises here.
+    """
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
+                 fused=None, classification=None):
+        from models.compnets.model_ccn import _CCN
+        if not isinstance(model, _CCN):
+            raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
+        if classification:
+            raise RuntimeError("hgnn_amd: CcnTrainStep has no classification branch (scripts/train_ccn.py:39-41)")
+        if t_mean is None:
+            raise RuntimeError("hgnn_amd: CcnTrainStep needs the target statistics t_mean and t_std")
+        if float(t_mean) == 0.0 and classification is None:
+            raise RuntimeError("hgnn_amd: t_mean == 0 selects the reference's classification branch "
+                               "(scripts/train_ccn.py:39-41), which CcnTrainStep does not have; pass "
+                               "classification=False for regression on targets of mean 0")
+        self.model = model
+        self.params = model._params()
+        dev = self.params[0].device
+        if dev.type != "cuda":
+            raise RuntimeError("hgnn_amd: CcnTrainStep runs on the GPU only (call model.cuda() first)")
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("hgnn_amd: CcnTrainStep needs contiguous float32 parameters")
+        self.lr = float(lr)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        self.weight_decay = float(weight_decay)
+        self.t_mean = float(t_mean)
+        self.t_std = float(t_std)
+        self.spec = model._spec()
+        self.fused = fused
+        if fused and not self._supported(1):
+            raise RuntimeError("hgnn_amd: fused=True needs CCN_1D with input_feats and hidden_size <= 8 "
+                               "(hgnn_ccn_small_train_supported)")
+        self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.out = None
+        self._grads = [torch.zeros_like(p) for p in self.params]
+        self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
+        # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
+        self._mean = torch.tensor(self.t_mean, dtype=torch.float32, device=dev)
+        self._div = torch.tensor(self.t_std + 1e-8, dtype=torch.float32, device=dev)
+        self.reset_optimizer()
+
+    def reset_optimizer(self):
+        """The driver builds a new Adamax every epoch (scripts/main_ccn_qm9.py:178): zero state, step 0."""
+        self.exp_avg = [torch.zeros_like(p) for p in self.params]
+        self.exp_inf = [torch.zeros_like(p) for p in self.params]
+        self.step_count = 0
+
+    def reset_running(self):
+        """New RunningAverage meters (one pair per train_ccn call, scripts/train_ccn.py:28-29)."""
+        self.stats.zero_()
+
+    def _supported(self, nmax):
+        cfg = self.spec.config(1, nmax)
+        return bool(L.lib().hgnn_ccn_small_train_supported(ctypes.byref(cfg)))
+
+    def _inputs(self, X, adj, n_batch, y):
+        from .ccn import _check_shapes
+        from .net import _f32, _i64, _require_cuda
+        _require_cuda([X, adj, n_batch, y, *self.params], "CCN training step")
+        X, adj = _f32(X), _f32(adj)
+        n_batch = None if n_batch is None else _i64(n_batch)
+        _check_shapes(self.spec, self.params, X, adj, n_batch)
+        G, n_out = X.shape[0], self.spec.n_out
+        if y.numel() != G * n_out:
+            raise RuntimeError(f"hgnn_amd: targets {tuple(y.shape)} do not match {G} graphs x {n_out} outputs")
+        return X, adj, n_batch, y.to(torch.float32).reshape(G, n_out).contiguous()
+
+    def step(self, X, adj, n_batch, y):
+        """One reference step per graph of the padded batch (forward_batch's layout: adj with self loops),
+        in index order; y: raw targets (G,) or (G, n_out).  Returns the device tensor `stats` = [loss, mae,
+        running loss, running mae] after the last graph; leaves .out (G, n_out), the output each graph saw
+        before its own update, and p.grad = the last graph's gradients."""
+        X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
+        G, nmax = X.shape[0], X.shape[1]
+        fused = self.fused
+        if fused is None:
+            fused = self._supported(nmax)
+        elif fused and not self._supported(nmax):
+            raise RuntimeError(f"hgnn_amd: fused=True, but nmax = {nmax} is outside the fused kernel's bounds "
+                               "(hgnn_ccn_small_train_supported)")
+        self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
+        if fused:
+            self._step_fused(X, adj, n_batch, y)
+        else:
+            self._step_unfused(X, adj, n_batch, y)
+        return self.stats
+
+    def _step_fused(self, X, adj, n_batch, y):
+        from .ccn import _word
+        from .net import _capturing, check_errors, strict
+        lib = L.lib()
+        check_errors(block=False)
+        dev = X.device
+        stream = L.stream_handle(dev)
+        b1, b2 = self.betas
+        for g0 in range(0, X.shape[0], CCN_TRAIN_MAX_GRAPHS):
+            g1 = min(g0 + CCN_TRAIN_MAX_GRAPHS, X.shape[0])
+            cfg = self.spec.config(g1 - g0, X.shape[1])
+            # the step sizes in double on the host, as hgnn_adamax_step forms its own; pinned, so the copy
+            # does not wait for the stream
+            clr = torch.tensor([self.lr / (1.0 - b1 ** t) for t in range(self.step_count + 1,
+                                                                         self.step_count + 1 + g1 - g0)],
+                               dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+            err, tag = _word.next(dev)
+            L.check(lib.hgnn_ccn_small_train(
+                ctypes.byref(cfg), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]), L.ptr(None if n_batch is None else n_batch[g0:g1]),
+                L.ptr(y[g0:g1]), self.t_mean, self.t_std, L.ptr_array(self.params), L.ptr_array(self._grads),
+                L.ptr_array(self.exp_avg), L.ptr_array(self.exp_inf), L.ptr(clr), b1, b2, self.eps,
+                self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), err, tag, stream),
+                "hgnn_ccn_small_train")
+            self.step_count += g1 - g0
+        for p, g in zip(self.params, self._grads):
+            p.grad = g
+        if strict() and not _capturing():
+            _word.check(True)
+
+    def _step_unfused(self, X, adj, n_batch, y):
+        lib = L.lib()
+        m = self.model
+        stream = L.stream_handle(X.device)
+        yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device: no per-graph host work
+        n_out = self.spec.n_out
+        for g in range(X.shape[0]):
+            for p in self.params:
+                p.grad = None
+            out = m.forward_batch(X[g:g + 1], adj[g:g + 1], None if n_batch is None else n_batch[g:g + 1])
+            dout = torch.empty_like(out)
+            L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(yn[g]), n_out, 0.0, 1.0, L.ptr(self.stats),
+                                      L.ptr(dout), stream), "mse loss")
+            torch.autograd.backward(out, dout)
+            grads = [p.grad for p in self.params]
+            if any(gr is None for gr in grads):
+                raise RuntimeError("hgnn_amd: a parameter received no gradient")
+            self.step_count += 1
+            L.check(lib.hgnn_adamax_step(len(self.params), L.ptr_array(self.params), L.ptr_array(grads),
+                                         L.ptr_array(self.exp_avg), L.ptr_array(self.exp_inf), self._numel, self.lr,
+                                         self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
+                                         stream), "adamax step")
+            self.out[g].copy_(out.detach()[0])
+
+    def evaluate(self, X, adj, n_batch, y):
+        """scripts/test_ccn.py:34-67 on a padded batch: one forward_batch, then the device tensor
+        [losses.avg, error.avg] (the plain means over the graphs of the per-graph MSE and MAE)."""
+        X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
+        with torch.no_grad():
+            out = self.model.forward_batch(X, adj, n_batch).contiguous()
+        res = torch.empty(2, dtype=torch.float32, device=X.device)
+        L.check(L.lib().hgnn_ccn_eval_loss(L.ptr(out), L.ptr(y), X.shape[0], self.spec.n_out, self.t_mean,
+                                           self.t_std, L.ptr(res), L.stream_handle(X.device)), "hgnn_ccn_eval_loss")
+        return res
+
+    def _chunks(self, data, task, chunk):
+        """The reference's list of 7-tuples (X, A, targets, ...) as padded device chunks: A + I
+        (train_ccn.py:36), each chunk padded to its largest graph."""
+        dev = self.params[0].device
+        f = self.spec.f_in
+        for c0 in range(0, len(data), chunk):
+            part = data[c0:c0 + chunk]
+            nmax = max(int(d[0].shape[0]) for d in part)
+            X = torch.zeros(len(part), nmax, f)
+            A = torch.zeros(len(part), nmax, nmax)
+            nb = torch.empty(len(part), dtype=torch.int64)
+            y = torch.empty(len(part), 1)
+            for b, d in enumerate(part):
+                n = int(d[0].shape[0])
+                X[b, :n] = d[0].detach().cpu()
+                A[b, :n, :n] = d[1].detach().cpu() + torch.eye(n)
+                nb[b] = n
+                y[b, 0] = d[2][task]
+            yield X.to(dev), A.to(dev), nb.to(dev), y.to(dev)
+
+    def train_epoch(self, data, task, chunk=1024):
+        """train_ccn(net, data, task, ...) (scripts/train_ccn.py:24-73): one step per graph in list order, new
+        meters; returns (losses.val, error.val), read once at the end."""
+        if self.spec.n_out != 1:
+            raise RuntimeError("hgnn_amd: train_epoch takes one target per graph (targets[task].view(1))")
+        self.reset_running()
+        for X, A, nb, y in self._chunks(data, task, chunk):
+            self.step(X, A, nb, y)
+        s = self.stats.tolist()
+        return s[2], s[3]
+
+    def eval_epoch(self, data, task, chunk=1024):
+        """test_ccn(ccn, data, task, ...) (scripts/test_ccn.py:23-67): (losses.avg, error.avg) over the list;
+        the chunks' means weighted by their graph counts, as AverageMeter.update(v, 1) per graph does."""
+        if self.spec.n_out != 1:
+            raise RuntimeError("hgnn_amd: eval_epoch takes one target per graph (targets[task].view(1))")
+        acc = None
+        for X, A, nb, y in self._chunks(data, task, chunk):
+            r = self.evaluate(X, A, nb, y).double() * X.shape[0]
+            acc = r if acc is None else acc + r
+        if acc is None:
+            return 0.0, 0.0
+        s = (acc / len(data)).tolist()
+        return s[0], s[1]

@@ -380,6 +380,38 @@ int hgnn_ccn_small_backward(const hgnn_ccn_config* cfg, const float* d_X, const 
                             const int64_t* d_n_batch, const float* const* params, void* workspace,
                             const float* d_dout, float* const* grads, float* d_dX, void* stream);
 
+/* The per-graph training loop of scripts/train_ccn.py:31-73 (per graph: the normalised target, net(X, A + I),
+ * MAE and MSE meters, backward, one Adamax step) for CCN_1D in ONE dispatch: one workgroup walks the cfg->bs
+ * graphs in index order -- forward, loss, backward and the optimizer step of graph g, then graph g + 1 on the
+ * weights graph g left -- with no host round trip.  The arithmetic is that of the pieces it replaces:
+ * hgnn_ccn_small_forward / _backward on the one-graph slice, hgnn_mse_loss on the normalised target and
+ * hgnn_adamax_step.
+ *   supported: host only; 1 for order 1 within hgnn_ccn_small_supported's bounds (cfg->bs is not looked at)
+ *     and n_out <= 1088, else 0.
+ *   cfg->bs = the number of graphs, 1 .. 4096 (HGNN_ERR_ARG above: split the list); d_X, d_adj, d_n_batch as
+ *     hgnn_ccn_small_forward (d_n_batch may be NULL); d_y (bs, n_out) raw targets, normalised as
+ *     (y - (float)t_mean) / (float)(t_std + 1e-8) (train_ccn.py:42).
+ *   params (updated in place), grads (left holding the last applied graph's gradients), exp_avg, exp_inf
+ *     (updated in place): 2 layers + 2 device pointers each, in the parameter order above.
+ *   d_clr (bs,): the step sizes (float)(lr / (1 - beta1^t)) of the steps t = step0 + 1, step0 + 2, ... this call
+ *     takes, formed in double as hgnn_adamax_step forms its own; entry k belongs to the k-th applied step.
+ *   d_stats[4]: loss, MAE and the RunningAverage of both, as hgnn_mse_loss updates them, once per graph.
+ *   d_out (bs, n_out): the output each graph saw before its own update.
+ *   A graph with validation bits (see above) gets its d_out row and *d_err = tag * 256 + bits, and nothing
+ *     else: no loss, no meters, no gradients, no step; the loop goes on with the next graph. */
+int hgnn_ccn_small_train_supported(const hgnn_ccn_config* cfg);
+int hgnn_ccn_small_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                         const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                         float* const* params, float* const* grads, float* const* exp_avg,
+                         float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
+                         double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag,
+                         void* stream);
+/* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
+ * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
+ * as above.  One block, fp64 sums in a fixed order: the same bits every call. */
+int hgnn_ccn_eval_loss(const float* d_out, const float* d_y, int n_graphs, int n_out, double t_mean,
+                       double t_std, float* d_res, void* stream);
+
 /* collapse6to3 (functions/contraction.py:106-121) on a general 6-D tensor
  * F (C, n, n, n, n, n) -> (n, n, 18 C); the 18 contractions of _c6to2_111 /
  * _c6to2_12 / _c6to2_3 with their diagonal filters. */

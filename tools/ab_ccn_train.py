@@ -1,0 +1,81 @@
+"""Same-process A/B of the per-graph CCN-1D training loop (scripts/train_ccn.py:31-73): epochs over the same 256
+QM9-shape graphs alternate between three paths,
+
+  torch     net(x, a), nn.MSELoss, torch.optim.Adamax per graph (the drop-in model under the reference's loop)
+  unfused   hgnn_amd.train.CcnTrainStep(fused=False): forward_batch, hgnn_mse_loss, backward, hgnn_adamax_step
+  fused     CcnTrainStep(fused=True): hgnn_ccn_small_train, one dispatch per epoch
+
+each on its own copy of CCN_1D(5, 1, 2, 2).  Per path the min and median ms per graph over the epochs, printed
+as one JSON line and written to profiles/ccn_train_ab.json.  The tool holds no expectation."""
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(REPO, "hgnn-2_amd"), REPO, os.path.join(REPO, "tools")]
+import torch  # noqa: E402
+
+MEAN, STD, LR = 0.3, 1.7, 1e-3
+
+
+def main():
+    import hgnn_amd.datagen as dg
+    from hgnn_amd.train import CcnTrainStep
+    from models.compnets.model_ccn import CCN_1D
+    graphs = dg.qm9_shape_dataset(256, seed=7)
+    torch.manual_seed(0)
+    nets = {"torch": CCN_1D(5, 1, 2, 2).cuda()}
+    nets["unfused"] = copy.deepcopy(nets["torch"])
+    nets["fused"] = copy.deepcopy(nets["torch"])
+    opt = torch.optim.Adamax(nets["torch"].parameters(), lr=LR)
+    crit = torch.nn.MSELoss()
+    data = [(x.cuda(), (a + torch.eye(a.shape[0])).cuda(), ((t[0].view(1) - MEAN) / (STD + 10 ** -8)).cuda())
+            for x, a, t in graphs]
+    nmax = max(x.shape[0] for x, _, _ in graphs)
+    X = torch.zeros(len(graphs), nmax, 5)
+    A = torch.zeros(len(graphs), nmax, nmax)
+    for b, (x, a, _) in enumerate(graphs):
+        n = x.shape[0]
+        X[b, :n] = x
+        A[b, :n, :n] = a + torch.eye(n)
+    X, A = X.cuda(), A.cuda()
+    nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64).cuda()
+    Y =torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
+    steps = {k: CcnTrainStep(nets[k], lr=LR, t_mean=MEAN, t_std=STD, fused=(k == "fused"))
+             for k in ("unfused", "fused")}
+
+    def torch_epoch():
+        net = nets["torch"]
+        for x, a, y in data:
+            opt.zero_grad()
+            loss = crit(net(x, a), y)
+            loss.backward()
+            opt.step()
+
+    paths = {"torch": torch_epoch, "unfused": lambda: steps["unfused"].step(X, A, nb, Y),
+             "fused": lambda: steps["fused"].step(X, A, nb, Y)}
+    times = {k: [] for k in paths}
+    for it in range(12):
+        for k, fn in paths.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if it >= 2:
+                times[k].append((time.perf_counter() - t0) * 1e3 / len(graphs))
+    res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5)}
+           for k, v in times.items()}
+    res["graphs"] = len(graphs)
+    res["epochs"] = len(times["fused"])
+    print(json.dumps(res))
+    os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
+    with open(os.path.join(REPO, "profiles", "ccn_train_ab.json"), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
