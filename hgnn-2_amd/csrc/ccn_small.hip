@@ -647,7 +647,10 @@ __device__ __forceinline__ float cs_fresh(const float* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int CF, int CH>
+// XENT: the reference's `mean == 0` branch (train_ccn.py:39-41, 56-57) -- y[g] is a class index, the loss is
+// nn.CrossEntropyLoss on the graph's row (xent_row, k_xent_loss's arithmetic with n = 1) and the MAE meters are
+// never written.  A template parameter, so the MSE instantiations keep their instructions.
+template <int CF, int CH, bool XENT>
 __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
@@ -697,6 +700,12 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t)
                 s.red[o] = ov;
             }
         }
+        // a target that is no class index rejects the graph like a validation bit: set before the barrier the
+        // read of sbad follows, so the branch below is block-uniform
+        int ti = 0;
+        if constexpr (XENT) {
+            if (threadIdx.x == 0 && !xent_target(t.y[g], n_out, ti)) atomicOr(&sbad, (uint32_t)ERR_CLASS_TARGET);
+        }
         __syncthreads();
         const uint32_t gbad = sbad;
         __syncthreads();
@@ -704,36 +713,49 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t)
             if (threadIdx.x == 0) a.err[0] = a.tag * 256 + (int)gbad;  // vector store (host-mapped word)
             continue;
         }
-        // 3. loss, meters and dout (k_mse_loss's arithmetic on the normalised target); dout replaces out in red
-        double se = 0.0, ae = 0.0;
-        if (threadIdx.x < CS_RT)
-            for (int i = threadIdx.x; i < n_out; i += CS_RT) {
-                const float yn = (t.y[(long long)g * n_out + i] - t.t_mean) / t.t_div;
-                const float d = s.red[i] - yn;
-                se += (double)d * d;
-                ae += fabs((double)d);
-                s.red[i] = 2.0f * d / (float)n_out;
+        // 3. loss, meters and dout; dout replaces out in red
+        if constexpr (XENT) {
+            // k_xent_loss's arithmetic on one row (n = 1: the mean is the row's loss, 1 / n = 1.0f), by one thread
+            // in the row function's serial order; stats[1] and stats[3] are never written (train_ccn.py:54-57)
+            if (threadIdx.x == 0) {
+                const float loss = (float)(double)xent_row(s.red, ti, n_out, 1.0f, s.red);
+                run_l = run_l == 0.f ? loss : 0.9f * loss + 0.1f * run_l;
+                t.stats[0] = loss;
+                t.stats[2] = run_l;
             }
-        se = wave_sum_d(se);
-        ae = wave_sum_d(ae);
-        if (lane == 0) {
-            s.dred[wv] = se;
-            s.dred[CS_NW + wv] = ae;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double S = 0.0, A = 0.0;
-            for (int i = 0; i < CS_RT / 64; ++i) {
-                S += s.dred[i];
-                A += s.dred[CS_NW + i];
+            __syncthreads();
+        } else {
+            // k_mse_loss's arithmetic on the normalised target
+            double se = 0.0, ae = 0.0;
+            if (threadIdx.x < CS_RT)
+                for (int i = threadIdx.x; i < n_out; i += CS_RT) {
+                    const float yn = (t.y[(long long)g * n_out + i] - t.t_mean) / t.t_div;
+                    const float d = s.red[i] - yn;
+                    se += (double)d * d;
+                    ae += fabs((double)d);
+                    s.red[i] = 2.0f * d / (float)n_out;
+                }
+            se = wave_sum_d(se);
+            ae = wave_sum_d(ae);
+            if (lane == 0) {
+                s.dred[wv] = se;
+                s.dred[CS_NW + wv] = ae;
             }
-            const float loss = (float)(S / n_out), mae = (float)(A / n_out);
-            run_l = run_l == 0.f ? loss : 0.9f * loss + 0.1f * run_l;
-            run_m = run_m == 0.f ? mae : 0.9f * mae + 0.1f * run_m;
-            t.stats[0] = loss;
-            t.stats[1] = mae;
-            t.stats[2] = run_l;
-            t.stats[3] = run_m;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                double S = 0.0, A = 0.0;
+                for (int i = 0; i < CS_RT / 64; ++i) {
+                    S += s.dred[i];
+                    A += s.dred[CS_NW + i];
+                }
+                const float loss = (float)(S / n_out), mae = (float)(A / n_out);
+                run_l = run_l == 0.f ? loss : 0.9f * loss + 0.1f * run_l;
+                run_m = run_m == 0.f ? mae : 0.9f * mae + 0.1f * run_m;
+                t.stats[0] = loss;
+                t.stats[1] = mae;
+                t.stats[2] = run_l;
+                t.stats[3] = run_m;
+            }
         }
         // 4. backward, k_ccn1_small_bwd's one-graph form: fc gradients from dout and feat, dsum, the levels
         const float* dob = s.red;
@@ -878,6 +900,67 @@ void cs_lds_attr(K kernel, bool& done) {
 
 using namespace hgnn;
 
+namespace {
+
+// Both training entries: the argument checks and the launch; XENT picks the loss stage (and ignores the target
+// statistics).
+template <bool XENT>
+int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
+             const float* d_y, double t_mean, double t_std, float* const* params, float* const* grads,
+             float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
+             double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag, void* stream) {
+    if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
+    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || !exp_inf || !d_clr || !d_stats || !d_out ||
+        !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > CS_TRAIN_GMAX || (XENT && cfg->n_out < 2))
+        return HGNN_ERR_ARG;
+    const int nt = 2 * cfg->layers + 2;
+    for (int k = 0; k < nt; ++k)
+        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_inf[k]) return HGNN_ERR_ARG;
+    CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, nullptr);
+    a.bs = 1;  // the one-graph form of the backward: gradients written directly; the kernel passes b = g
+    a.out = d_out;
+    a.err = d_err;
+    a.tag = tag;
+    for (int l = 0; l < cfg->layers; ++l) {
+        a.gW[l] = grads[2 * l];
+        a.gB[l] = grads[2 * l + 1];
+    }
+    a.gfcw = grads[2 * cfg->layers];
+    a.gfcb = grads[2 * cfg->layers + 1];
+    CsTrain t{};
+    t.y = d_y;
+    t.clr = d_clr;
+    // scalars combine in double and reach the kernel as fp32, as the reference's Python floats reach torch
+    t.t_mean = (float)t_mean;
+    t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
+    t.w = (float)(1.0 - beta1);
+    t.beta2 = (float)beta2;
+    t.eps = (float)eps;
+    t.wd = (float)weight_decay;
+    for (int k = 0; k < nt; ++k) {
+        t.p[k] = params[k];
+        t.m[k] = exp_avg[k];
+        t.u[k] = exp_inf[k];
+    }
+    t.stats = d_stats;
+    t.G = cfg->bs;
+    const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, true);
+    hipStream_t s = (hipStream_t)stream;
+    if (cfg->hidden <= 2) {
+        static bool attr = false;
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2, XENT>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2, XENT>), dim3(1), dim3(CS_NT), lds, s, a, t);
+    } else {
+        static bool attr = false;
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF, XENT>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF, XENT>), dim3(1), dim3(CS_NT), lds, s, a, t);
+    }
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int hgnn_ccn_small_supported(const hgnn_ccn_config* cfg) {
@@ -996,54 +1079,17 @@ int hgnn_ccn_small_train(const hgnn_ccn_config* cfg, const float* d_X, const flo
                          float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
                          double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
                          int32_t* d_err, int32_t tag, void* stream) {
-    if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
-    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || !exp_inf || !d_clr || !d_stats || !d_out ||
-        !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > CS_TRAIN_GMAX)
-        return HGNN_ERR_ARG;
-    const int nt = 2 * cfg->layers + 2;
-    for (int k = 0; k < nt; ++k)
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_inf[k]) return HGNN_ERR_ARG;
-    CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, nullptr);
-    a.bs = 1;  // the one-graph form of the backward: gradients written directly; the kernel passes b = g
-    a.out = d_out;
-    a.err = d_err;
-    a.tag = tag;
-    for (int l = 0; l < cfg->layers; ++l) {
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gfcw = grads[2 * cfg->layers];
-    a.gfcb = grads[2 * cfg->layers + 1];
-    CsTrain t{};
-    t.y = d_y;
-    t.clr = d_clr;
-    // scalars combine in double and reach the kernel as fp32, as the reference's Python floats reach torch
-    t.t_mean = (float)t_mean;
-    t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
-    t.w = (float)(1.0 - beta1);
-    t.beta2 = (float)beta2;
-    t.eps = (float)eps;
-    t.wd = (float)weight_decay;
-    for (int k = 0; k < nt; ++k) {
-        t.p[k] = params[k];
-        t.m[k] = exp_avg[k];
-        t.u[k] = exp_inf[k];
-    }
-    t.stats = d_stats;
-    t.G = cfg->bs;
-    const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, true);
-    hipStream_t s = (hipStream_t)stream;
-    if (cfg->hidden <= 2) {
-        static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2>), dim3(1), dim3(CS_NT), lds, s, a, t);
-    } else {
-        static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF>), dim3(1), dim3(CS_NT), lds, s, a, t);
-    }
-    HGNN_LAUNCH_CHECK();
-    return HGNN_OK;
+    return cs_train<false>(cfg, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, grads, exp_avg, exp_inf, d_clr,
+                           beta1, beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream);
+}
+
+int hgnn_ccn_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                              const int64_t* d_n_batch, const float* d_y, float* const* params, float* const* grads,
+                              float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
+                              double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
+                              int32_t* d_err, int32_t tag, void* stream) {
+    return cs_train<true>(cfg, d_X, d_adj, d_n_batch, d_y, 0.0, 1.0, params, grads, exp_avg, exp_inf, d_clr, beta1,
+                          beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream);
 }
 
 }  // extern "C"

@@ -515,6 +515,30 @@ __device__ __forceinline__ void adamax_elem(float& p, float g, float& m, float& 
     p = p + (-lr_c) * (m / u);  // addcdiv_(m, u, value = -clr)
 }
 
+// ---------------------------------------------------------------- cross-entropy
+// One row of nn.CrossEntropyLoss on c logits (train.hip): the class index of a target stored as float (a
+// LongTensor cast truncates toward zero); false if it is no integer in [0, c).
+__device__ __forceinline__ bool xent_target(float y, int c, int& ti) {
+    ti = (int)y;
+    return !(ti < 0 || ti >= c || (float)ti != y);
+}
+
+// The row's loss logsumexp(x) - x[ti] in a serial order over the classes (max, sum of expf(x - max), lse = max +
+// logf(sum)) and, when dout is given, dout[k] = (softmax(x)[k] - onehot(ti)[k]) * inv.  dout may be x itself:
+// x[ti] is read first and element k is written after its last read.  The one definition of the row: k_xent_loss,
+// k_ccn_eval_xent and the CCN training kernel (ccn_small.hip) all inline it.
+__device__ __forceinline__ float xent_row(const float* x, int ti, int c, float inv, float* dout) {
+    float m = x[0];
+    for (int k = 1; k < c; ++k) m = fmaxf(m, x[k]);
+    float s = 0.f;
+    for (int k = 0; k < c; ++k) s += expf(x[k] - m);
+    const float lse = m + logf(s);
+    const float nll = lse - x[ti];
+    if (dout)
+        for (int k = 0; k < c; ++k) dout[k] = (expf(x[k] - lse) - (k == ti ? 1.f : 0.f)) * inv;
+    return nll;
+}
+
 // CCN-2D one-workgroup-per-graph path (ccn2_small.hip) behind hgnn_ccn_small_* for order 2
 bool ccn2_small_ok(const hgnn_ccn_config* c);
 size_t ccn2_small_workspace_bytes(const hgnn_ccn_config* c);

@@ -67,24 +67,15 @@ __global__ void __launch_bounds__(256) k_xent_loss(const float* __restrict__ out
     double se = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
         const float* x = out + (long long)i * c;
-        const int ti = (int)t[i];  // LongTensor cast truncates toward zero
-        if (ti < 0 || ti >= c || (float)ti != t[i]) {
+        int ti;
+        if (!xent_target(t[i], c, ti)) {
             // a rejected row contributes nothing: its dout row is zero, never uninitialised memory
             atomicOr(err, 1u);
             if (dout)
                 for (int k = 0; k < c; ++k) dout[(long long)i * c + k] = 0.f;
             continue;
         }
-        float m = x[0];
-        for (int k = 1; k < c; ++k) m = fmaxf(m, x[k]);
-        float s = 0.f;
-        for (int k = 0; k < c; ++k) s += expf(x[k] - m);
-        const float lse = m + logf(s);
-        se += (double)(lse - x[ti]);
-        if (dout) {
-            const float inv = 1.0f / (float)n;
-            for (int k = 0; k < c; ++k) dout[(long long)i * c + k] = (expf(x[k] - lse) - (k == ti ? 1.f : 0.f)) * inv;
-        }
+        se += (double)xent_row(x, ti, c, 1.0f / (float)n, dout ? dout + (long long)i * c : nullptr);
     }
     se = wave_sum_d(se);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = se;
@@ -158,6 +149,45 @@ __global__ void __launch_bounds__(256) k_ccn_eval_loss(const float* __restrict__
     }
 }
 
+// The classification branch of the same loop (test_ccn.py:40-41, 52-55: the target cast to a class index, the
+// output viewed as (1, n_out), nn.CrossEntropyLoss): [mean_g xent_g, 0, accuracy].  error.avg is never updated
+// on that branch and stays 0; the accuracy counts the graphs whose first maximum (torch.argmax's tie rule) is
+// the target.  A target that is no class index is reported and adds to neither sum; the divisor stays G.  One
+// block, fp64 sums in k_ccn_eval_loss's fixed order.
+__global__ void __launch_bounds__(256) k_ccn_eval_xent(const float* __restrict__ out, const float* __restrict__ y,
+                                                       int G, int c, float* __restrict__ res,
+                                                       uint32_t* __restrict__ err) {
+    __shared__ double red[2][4];
+    double se = 0.0, hit = 0.0;
+    for (int g = threadIdx.x; g < G; g += 256) {
+        const float* x = out + (long long)g * c;
+        int ti;
+        if (!xent_target(y[g], c, ti)) {
+            atomicOr(err, 1u);
+            continue;
+        }
+        se += (double)xent_row(x, ti, c, 1.0f, nullptr);
+        int am = 0;
+        for (int k = 1; k < c; ++k)
+            if (x[k] > x[am]) am = k;
+        hit += am == ti ? 1.0 : 0.0;
+    }
+    se = wave_sum_d(se);
+    hit = wave_sum_d(hit);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = se;
+        red[1][threadIdx.x >> 6] = hit;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double S = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        const double H = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        res[0] = G > 0 ? (float)(S / G) : 0.f;
+        res[1] = 0.f;
+        res[2] = G > 0 ? (float)(H / G) : 0.f;
+    }
+}
+
 }  // namespace
 }  // namespace hgnn
 
@@ -189,6 +219,15 @@ int hgnn_ccn_eval_loss(const float* d_out, const float* d_y, int n_graphs, int n
     const float div = (float)(t_std + 1e-8);  // std + 10 ** -8 in double, then fp32 (test_ccn.py:43)
     HGNN_KLAUNCH(k_ccn_eval_loss, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_y, n_graphs,
                        n_out, (float)t_mean, div, d_res);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+int hgnn_ccn_eval_xent(const float* d_out, const float* d_y, int n_graphs, int n_out, float* d_res, uint32_t* d_err,
+                       void* stream) {
+    if (!d_out || !d_y || !d_res || !d_err || n_graphs < 0 || n_out < 1) return HGNN_ERR_ARG;
+    HGNN_KLAUNCH(k_ccn_eval_xent, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_y, n_graphs,
+                       n_out, d_res, d_err);
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
 }

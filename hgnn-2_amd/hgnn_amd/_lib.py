@@ -30,6 +30,8 @@ DEVERR = {
     0x40: ("operator slice 0 or 1 (graph_operators' I and D, functions/operators.py:19-23) holds an off-diagonal "
            "entry, which the opt-in HGNN_DIAG_ID=1 form (these two slices taken as diagonal) cannot take -- unset "
            "HGNN_DIAG_ID (the default aggregates them as general slices)"),
+    0x80: ("class target outside [0, n_outputs) or not an integer (CCN training loop, scripts/train_ccn.py:39-41: "
+           "the graph took no step)"),
 }
 
 
@@ -123,7 +125,11 @@ SIGNATURES = {
     "hgnn_ccn_small_train": ([ctypes.POINTER(CcnConfig), _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, _VP,
                               _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                               ctypes.c_double, _VP, _VP, _VP, _I, _VP], _I),
+    "hgnn_ccn_small_train_xent": ([ctypes.POINTER(CcnConfig), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
+                                   _I, _VP], _I),
     "hgnn_ccn_eval_loss": ([_VP, _VP, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP], _I),
+    "hgnn_ccn_eval_xent": ([_VP, _VP, _I, _I, _VP, _VP, _VP], _I),
     "hgnn_collapse6to3": ([_VP, _VP, _I, _I, _VP], _I),
     "hgnn_collapse6to3_backward": ([_VP, _VP, _I, _I, _VP], _I),
     "hgnn_ccn_plan_offsets": ([ctypes.POINTER(CcnConfig), ctypes.c_longlong, ctypes.POINTER(ctypes.c_size_t)], _I),

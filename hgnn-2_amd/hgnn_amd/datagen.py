@@ -10,12 +10,17 @@ statistics SURVEY.md §8 d fixes:
 * SBM: two equal blocks (z = i mod 2), p_in / p_out, symmetric, no self loops,
   one-hot(min(deg, 4)) node features (5 features).
 
-Each generator returns a list of ``(X (N, f), A (N, N), t (13,))`` float32
+* Three collinear points: the reference's own generated data set
+  (`functions/data_generator.py:45-87`), the classification task of
+  `scripts/main_generate_ccn.py`; it returns the reference's 7-tuples.
+
+The first two generators return a list of ``(X (N, f), A (N, N), t (13,))`` float32
 tensors -- the first three members of the reference's 7-tuple instances
 (`functions/data_generator.py:85`, `preprocessing/preprocessing.py:95-97`).
 The operator members are produced by ``functions.operators.graph_operators``.
 
-This module imports nothing but torch/random so the golden-fixture script can
+This module imports nothing but torch/random at load time (three_collinear_points
+imports functions.operators only when asked for the operators) so the golden-fixture script can
 load it next to the reference without a package-name clash.
 """
 
@@ -78,3 +83,37 @@ def sbm_graph(gen, n=50, p_in=0.3, p_out=0.05, n_feat=5, n_targets=13):
 def sbm_dataset(n_graphs, n=50, seed=0, **kw):
     gen = torch.Generator().manual_seed(seed)
     return [sbm_graph(gen, n=n, **kw) for _ in range(n_graphs)]
+
+
+def three_collinear_points(n, n_max=50, d=5, p=0.5, c=0.5, seed=0, operators=False):
+    """The generated data set of functions/data_generator.py:45-87: n random graphs of 3 + randint(0, n_max - 3)
+    nodes (3 .. n_max - 1) with d random normal features per node.  With probability p a graph has label 1: three
+    of its rows are multiples 10 * randn(1) * x of one direction x = randn(1, d), placed among the random rows at
+    shuffled positions.  A = (rand > c), A[0, 1] = 1, symmetrised with min(A + A^T, 1); the diagonal may be 1
+    (and 2 once the driver adds I: the CCN drop-in goes by the pattern A > 0).
+
+    Returns the reference's instances [X, A, LongTensor([label]), W, WL, Pm, Pd]; the operators are
+    functions.operators.graph_operators([X, A], dual=True) when operators=True, else None (the CCN drivers
+    ignore them).  Everything is drawn from one torch.Generator seeded with `seed`; the reference draws from the
+    global RNG and random.shuffle, so its data is matched in distribution, not bit for bit."""
+    gen = torch.Generator().manual_seed(seed)
+    y = torch.rand(n, generator=gen) < p
+    extra = torch.randint(0, n_max - 3, (n,), generator=gen)
+    if operators:
+        from functions.operators import graph_operators
+    data = []
+    for i in range(n):
+        ni = int(extra[i])
+        if bool(y[i]):
+            x = torch.randn(1, d, generator=gen)
+            pts = [10 * torch.randn(1, generator=gen) * x for _ in range(3)]
+            rows = torch.cat([torch.randn(ni, d, generator=gen)] + pts, dim=0)
+            X = rows[torch.randperm(ni + 3, generator=gen)].contiguous()
+        else:
+            X = torch.randn(3 + ni, d, generator=gen)
+        A = (torch.rand(3 + ni, 3 + ni, generator=gen) > c).float()
+        A[0, 1] = 1.0
+        A = torch.clamp(A + A.t(), max=1.0)
+        ops = graph_operators([X, A], dual=True) if operators else (None, None, None, None)
+        data.append([X, A, torch.tensor([int(y[i])], dtype=torch.int64), *ops])
+    return data

@@ -27,6 +27,53 @@ import torch
 from . import _lib as L
 
 
+class _TargetWord:
+    """The error word of the cross-entropy kernels (a class target outside [0, dim_output) or not an integer ORs 1
+    into it), checked without synchronising the stream: watch() copies it to pinned memory behind an event, poll()
+    at the next step reads the copy once the event has completed.  HGNN_STRICT=1: watch() reads the word at once
+    (a host sync).  Shared by TrainStep and CcnTrainStep."""
+
+    MESSAGE = "hgnn_amd: class target outside [0, dim_output) or not an integer"
+
+    def __init__(self, dev):
+        self.dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        self.ev = None
+
+    def watch(self):
+        """After the kernels that may have set the word."""
+        if os.environ.get("HGNN_STRICT", "0") == "1":
+            self.ev = None
+            if int(self.dev.item()):
+                self.dev.zero_()
+                raise RuntimeError(self.MESSAGE)
+        elif not torch.cuda.is_current_stream_capturing():
+            self.host.copy_(self.dev, non_blocking=True)
+            self.ev = torch.cuda.Event()
+            self.ev.record()
+
+    def poll(self, block):
+        ev = self.ev
+        if ev is None:
+            return
+        if block:
+            ev.synchronize()
+        elif not ev.query():
+            return
+        self.ev = None
+        if int(self.host[0]):
+            self.dev.zero_()
+            self.host.zero_()
+            raise RuntimeError(self.MESSAGE + " (the rows were left out of the loss and gradients)")
+
+    def check(self):
+        """Raise if a watched kernel saw a bad target (host sync)."""
+        self.poll(block=True)
+        if int(self.dev.item()):
+            self.dev.zero_()
+            raise RuntimeError(self.MESSAGE)
+
+
 class TrainStep:
     """One train_with_mnb minibatch step for a GNN_lg / GNN_simple drop-in model.
 
@@ -59,11 +106,9 @@ class TrainStep:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("hgnn_amd: TrainStep needs contiguous float32 parameters")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
-        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
-        # the class-target error word, copied to pinned memory behind an event and checked at the
-        # next step without synchronising the stream (HGNN_STRICT=1: checked at once)
-        self._err_host = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        self._err_ev = None
+        # the class-target error word, checked at the next step without synchronising the stream
+        # (HGNN_STRICT=1: checked at once)
+        self._targets = _TargetWord(dev)
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
         self.reset_optimizer()
 
@@ -91,24 +136,9 @@ class TrainStep:
             out = m([X, W], Nb, mask)
         return out, T
 
-    def _poll_targets(self, block):
-        ev = self._err_ev
-        if ev is None:
-            return
-        if block:
-            ev.synchronize()
-        elif not ev.query():
-            return
-        self._err_ev = None
-        if int(self._err_host[0]):
-            self._err.zero_()
-            self._err_host.zero_()
-            raise RuntimeError("hgnn_amd: class target outside [0, dim_output) or not an integer "
-                               "(the rows were left out of the loss and gradients)")
-
     def __call__(self, batch):
         lib = L.lib()
-        self._poll_targets(block=False)
+        self._targets.poll(block=False)
         self.model.train()
         for p in self.params:
             p.grad = None
@@ -123,16 +153,8 @@ class TrainStep:
             if T.numel() != out.shape[0]:
                 raise RuntimeError(f"hgnn_amd: class targets {tuple(T.shape)} do not match {out.shape[0]} rows")
             L.check(lib.hgnn_xent_loss(L.ptr(out.detach()), L.ptr(T), out.shape[0], out.shape[1], L.ptr(self.stats),
-                                       L.ptr(dout), L.ptr(self._err), stream), "cross-entropy loss")
-            if os.environ.get("HGNN_STRICT", "0") == "1":
-                self._err_ev = None
-                if int(self._err.item()):
-                    self._err.zero_()
-                    raise RuntimeError("hgnn_amd: class target outside [0, dim_output) or not an integer")
-            elif not torch.cuda.is_current_stream_capturing():
-                self._err_host.copy_(self._err, non_blocking=True)
-                self._err_ev = torch.cuda.Event()
-                self._err_ev.record()
+                                       L.ptr(dout), L.ptr(self._targets.dev), stream), "cross-entropy loss")
+            self._targets.watch()
         else:
             if T.numel() != out.numel():
                 raise RuntimeError(f"hgnn_amd: targets {tuple(T.shape)} do not match the output {tuple(out.shape)}")
@@ -153,10 +175,7 @@ class TrainStep:
 
     def check_targets(self):
         """Raise if a classification step saw a target outside [0, dim_output) (host sync)."""
-        self._poll_targets(block=True)
-        if int(self._err.item()):
-            self._err.zero_()
-            raise RuntimeError("hgnn_amd: class target outside [0, dim_output) or not an integer")
+        self._targets.check()
 
 
 CCN_TRAIN_MAX_GRAPHS = 4096  # csrc/ccn_small.hip CS_TRAIN_GMAX: graphs per hgnn_ccn_small_train dispatch
@@ -183,8 +202,18 @@ class CcnTrainStep:
     step and updates no meter; the error shows at the next check (hgnn_amd.net.check_errors(), or at once
     under HGNN_STRICT=1).  step_count still counts it, so later step sizes then differ from a run without it.
 
-    Only the regression branch (mean != 0) is built: the reference's `mean == 0` class-target branch
-    (train_ccn.py:39-41, 56-57) raises here.
+    Classification (the reference's `mean == 0` branch, train_ccn.py:39-41, 56-57, the generated-data driver
+    scripts/main_generate_ccn.py): classification=True, or classification=None with t_mean == 0.0 as in
+    TrainStep.  y then holds one class index per graph, the loss is nn.CrossEntropyLoss on the graph's output
+    viewed as (1, n_outputs), and the MAE meters stats[1] and stats[3] are never written.  The fused path is
+    hgnn_ccn_small_train_xent, the unfused path uses hgnn_xent_loss with n = 1.  A target that is not an
+    integer in [0, n_outputs) raises the class-target error at the next check (the next step,
+    check_targets(), or at once under HGNN_STRICT=1) on both paths, which otherwise differ on such a graph:
+    the fused kernel skips it like a rejected graph (no step), the unfused path does what TrainStep does (the
+    row's dout is zero and the Adamax step is still taken, on zero gradients).
+
+    fused=None and classification: the kernel's backward LDS layout bounds the graph size by the depth (at the
+    generated driver's CCN_1D(5, 2, 2, 10): 31 nodes), so a chunk padded to a larger graph runs unfused.
     """
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
@@ -192,14 +221,17 @@ class CcnTrainStep:
         from models.compnets.model_ccn import _CCN
         if not isinstance(model, _CCN):
             raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
-        if classification:
-            raise RuntimeError("hgnn_amd: CcnTrainStep has no classification branch (scripts/train_ccn.py:39-41)")
+        # the reference's rule (train_ccn.py:39): mean == 0 marks generated (classification) data
+        if classification is None:
+            classification = t_mean is not None and float(t_mean) == 0.0
+        self.classification = bool(classification)
+        if self.classification and model.n_outputs < 2:
+            raise RuntimeError("hgnn_amd: classification needs n_outputs >= 2 (cross-entropy over one class is "
+                               "identically 0); pass t_mean != 0 or classification=False for regression")
         if t_mean is None:
-            raise RuntimeError("hgnn_amd: CcnTrainStep needs the target statistics t_mean and t_std")
-        if float(t_mean) == 0.0 and classification is None:
-            raise RuntimeError("hgnn_amd: t_mean == 0 selects the reference's classification branch "
-                               "(scripts/train_ccn.py:39-41), which CcnTrainStep does not have; pass "
-                               "classification=False for regression on targets of mean 0")
+            if not self.classification:
+                raise RuntimeError("hgnn_amd: CcnTrainStep needs the target statistics t_mean and t_std")
+            t_mean = 0.0
         self.model = model
         self.params = model._params()
         dev = self.params[0].device
@@ -226,6 +258,7 @@ class CcnTrainStep:
         # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
         self._mean = torch.tensor(self.t_mean, dtype=torch.float32, device=dev)
         self._div = torch.tensor(self.t_std + 1e-8, dtype=torch.float32, device=dev)
+        self._targets = _TargetWord(dev)  # the unfused classification path's and evaluate's error word
         self.reset_optimizer()
 
     def reset_optimizer(self):
@@ -250,15 +283,21 @@ class CcnTrainStep:
         n_batch = None if n_batch is None else _i64(n_batch)
         _check_shapes(self.spec, self.params, X, adj, n_batch)
         G, n_out = X.shape[0], self.spec.n_out
+        if self.classification:
+            if y.numel() != G:
+                raise RuntimeError(f"hgnn_amd: class targets {tuple(y.shape)} do not match {G} graphs")
+            return X, adj, n_batch, y.to(torch.float32).reshape(G).contiguous()
         if y.numel() != G * n_out:
             raise RuntimeError(f"hgnn_amd: targets {tuple(y.shape)} do not match {G} graphs x {n_out} outputs")
         return X, adj, n_batch, y.to(torch.float32).reshape(G, n_out).contiguous()
 
     def step(self, X, adj, n_batch, y):
         """One reference step per graph of the padded batch (forward_batch's layout: adj with self loops),
-        in index order; y: raw targets (G,) or (G, n_out).  Returns the device tensor `stats` = [loss, mae,
-        running loss, running mae] after the last graph; leaves .out (G, n_out), the output each graph saw
-        before its own update, and p.grad = the last graph's gradients."""
+        in index order; y: raw targets (G,) or (G, n_out) -- classification: G class indices of any dtype.
+        Returns the device tensor `stats` = [loss, mae, running loss, running mae] after the last graph; leaves
+        .out (G, n_out), the output each graph saw before its own update, and p.grad = the last graph's
+        gradients."""
+        self._targets.poll(block=False)
         X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
         G, nmax = X.shape[0], X.shape[1]
         fused = self.fused
@@ -291,12 +330,15 @@ class CcnTrainStep:
                                                                          self.step_count + 1 + g1 - g0)],
                                dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
             err, tag = _word.next(dev)
-            L.check(lib.hgnn_ccn_small_train(
-                ctypes.byref(cfg), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]), L.ptr(None if n_batch is None else n_batch[g0:g1]),
-                L.ptr(y[g0:g1]), self.t_mean, self.t_std, L.ptr_array(self.params), L.ptr_array(self._grads),
-                L.ptr_array(self.exp_avg), L.ptr_array(self.exp_inf), L.ptr(clr), b1, b2, self.eps,
-                self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), err, tag, stream),
-                "hgnn_ccn_small_train")
+            head = (ctypes.byref(cfg), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]),
+                    L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]))
+            tail = (L.ptr_array(self.params), L.ptr_array(self._grads), L.ptr_array(self.exp_avg),
+                    L.ptr_array(self.exp_inf), L.ptr(clr), b1, b2, self.eps, self.weight_decay, L.ptr(self.stats),
+                    L.ptr(self.out[g0:g1]), err, tag, stream)
+            if self.classification:
+                L.check(lib.hgnn_ccn_small_train_xent(*head, *tail), "hgnn_ccn_small_train_xent")
+            else:
+                L.check(lib.hgnn_ccn_small_train(*head, self.t_mean, self.t_std, *tail), "hgnn_ccn_small_train")
             self.step_count += g1 - g0
         for p, g in zip(self.params, self._grads):
             p.grad = g
@@ -307,15 +349,21 @@ class CcnTrainStep:
         lib = L.lib()
         m = self.model
         stream = L.stream_handle(X.device)
-        yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device: no per-graph host work
+        cls = self.classification
+        if not cls:
+            yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device: no per-graph host work
         n_out = self.spec.n_out
         for g in range(X.shape[0]):
             for p in self.params:
                 p.grad = None
             out = m.forward_batch(X[g:g + 1], adj[g:g + 1], None if n_batch is None else n_batch[g:g + 1])
             dout = torch.empty_like(out)
-            L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(yn[g]), n_out, 0.0, 1.0, L.ptr(self.stats),
-                                      L.ptr(dout), stream), "mse loss")
+            if cls:  # the output viewed as (1, n_out) (train_ccn.py:57): one row of n_out classes
+                L.check(lib.hgnn_xent_loss(L.ptr(out.detach()), L.ptr(y[g:g + 1]), 1, n_out, L.ptr(self.stats),
+                                           L.ptr(dout), L.ptr(self._targets.dev), stream), "cross-entropy loss")
+            else:
+                L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(yn[g]), n_out, 0.0, 1.0, L.ptr(self.stats),
+                                          L.ptr(dout), stream), "mse loss")
             torch.autograd.backward(out, dout)
             grads = [p.grad for p in self.params]
             if any(gr is None for gr in grads):
@@ -326,13 +374,32 @@ class CcnTrainStep:
                                          self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
                                          stream), "adamax step")
             self.out[g].copy_(out.detach()[0])
+        if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
+            self._targets.watch()
+
+    def check_targets(self):
+        """Raise if a classification step or evaluation saw a target outside [0, n_outputs) (host sync): the
+        unfused path's and evaluate's error word, then the fused kernel's (hgnn_amd.net.check_errors())."""
+        from .net import check_errors
+        self._targets.check()
+        check_errors()
 
     def evaluate(self, X, adj, n_batch, y):
         """scripts/test_ccn.py:34-67 on a padded batch: one forward_batch, then the device tensor
-        [losses.avg, error.avg] (the plain means over the graphs of the per-graph MSE and MAE)."""
+        [losses.avg, error.avg] (the plain means over the graphs of the per-graph MSE and MAE).
+        Classification: [losses.avg, 0, accuracy] -- the mean per-graph cross entropy, error.avg as the
+        reference leaves it, and the fraction of graphs whose argmax is the target (hgnn_ccn_eval_xent)."""
         X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
         with torch.no_grad():
             out = self.model.forward_batch(X, adj, n_batch).contiguous()
+        if self.classification:
+            self._targets.poll(block=False)
+            res = torch.empty(3, dtype=torch.float32, device=X.device)
+            L.check(L.lib().hgnn_ccn_eval_xent(L.ptr(out), L.ptr(y), X.shape[0], self.spec.n_out, L.ptr(res),
+                                               L.ptr(self._targets.dev), L.stream_handle(X.device)),
+                    "hgnn_ccn_eval_xent")
+            self._targets.watch()
+            return res
         res = torch.empty(2, dtype=torch.float32, device=X.device)
         L.check(L.lib().hgnn_ccn_eval_loss(L.ptr(out), L.ptr(y), X.shape[0], self.spec.n_out, self.t_mean,
                                            self.t_std, L.ptr(res), L.stream_handle(X.device)), "hgnn_ccn_eval_loss")
@@ -349,7 +416,7 @@ class CcnTrainStep:
             X = torch.zeros(len(part), nmax, f)
             A = torch.zeros(len(part), nmax, nmax)
             nb = torch.empty(len(part), dtype=torch.int64)
-            y = torch.empty(len(part), 1)
+            y = torch.empty(len(part), 1)  # one value per graph: targets[task].view(1)
             for b, d in enumerate(part):
                 n = int(d[0].shape[0])
                 X[b, :n] = d[0].detach().cpu()
@@ -360,25 +427,30 @@ class CcnTrainStep:
 
     def train_epoch(self, data, task, chunk=1024):
         """train_ccn(net, data, task, ...) (scripts/train_ccn.py:24-73): one step per graph in list order, new
-        meters; returns (losses.val, error.val), read once at the end."""
-        if self.spec.n_out != 1:
+        meters; returns (losses.val, error.val), read once at the end.  Classification: targets[task] is the
+        class index, n_outputs >= 2, and error.val is the 0.0 the reference's untouched meter returns."""
+        if self.spec.n_out != 1 and not self.classification:
             raise RuntimeError("hgnn_amd: train_epoch takes one target per graph (targets[task].view(1))")
         self.reset_running()
         for X, A, nb, y in self._chunks(data, task, chunk):
             self.step(X, A, nb, y)
         s = self.stats.tolist()
-        return s[2], s[3]
+        return (s[2], 0.0) if self.classification else (s[2], s[3])
 
-    def eval_epoch(self, data, task, chunk=1024):
+    def eval_epoch(self, data, task, chunk=1024, accuracy=False):
         """test_ccn(ccn, data, task, ...) (scripts/test_ccn.py:23-67): (losses.avg, error.avg) over the list;
-        the chunks' means weighted by their graph counts, as AverageMeter.update(v, 1) per graph does."""
-        if self.spec.n_out != 1:
+        the chunks' means weighted by their graph counts, as AverageMeter.update(v, 1) per graph does.
+        Classification: (losses.avg, 0.0) as the reference returns; accuracy=True adds the accuracy as a third
+        value."""
+        if accuracy and not self.classification:
+            raise RuntimeError("hgnn_amd: eval_epoch(accuracy=True) needs a classification step")
+        if self.spec.n_out != 1 and not self.classification:
             raise RuntimeError("hgnn_amd: eval_epoch takes one target per graph (targets[task].view(1))")
         acc = None
         for X, A, nb, y in self._chunks(data, task, chunk):
             r = self.evaluate(X, A, nb, y).double() * X.shape[0]
             acc = r if acc is None else acc + r
         if acc is None:
-            return 0.0, 0.0
+            return (0.0, 0.0, 0.0) if accuracy else (0.0, 0.0)
         s = (acc / len(data)).tolist()
-        return s[0], s[1]
+        return (s[0], s[1], s[2]) if accuracy else (s[0], s[1])

@@ -64,6 +64,7 @@ extern "C" {
 #define HGNN_DEVERR_CCN_DEGREE 0x10u  /* CCN degree above the compiled bound    */
 #define HGNN_DEVERR_CCN_ASYM 0x20u    /* CCN adjacency pattern not symmetric    */
 #define HGNN_DEVERR_DIAG_ID 0x40u     /* operator slice 0 / 1 (I, D) not diagonal */
+#define HGNN_DEVERR_CLASS_TARGET 0x80u /* CCN loop: class target not an integer in [0, n_out) */
 
 int hgnn_abi_version(void);
 const char* hgnn_status_string(int status);
@@ -406,11 +407,32 @@ int hgnn_ccn_small_train(const hgnn_ccn_config* cfg, const float* d_X, const flo
                          float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
                          double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag,
                          void* stream);
+/* The same loop on the reference's classification branch (`mean == 0`, scripts/train_ccn.py:39-41, 56-57: the
+ * target cast to a class index, the output viewed as (1, n_out), nn.CrossEntropyLoss; the generated-data driver
+ * scripts/main_generate_ccn.py).  Arguments as hgnn_ccn_small_train without the target statistics, and:
+ *   d_y (bs,): class indices stored as float; cfg->n_out >= 2 (HGNN_ERR_ARG below: one class has loss 0).
+ *   The loss of a graph is hgnn_xent_loss's on its row (n = 1), bit for bit: both kernels inline one row function.
+ *   d_stats[0] = the graph's cross entropy, d_stats[2] its RunningAverage; d_stats[1] and d_stats[3] are never
+ *     written (no MAE on this branch).
+ *   A target that is not an integer in [0, n_out) is handled like a validation bit: the graph gets its d_out
+ *     row and *d_err = tag * 256 + bits with HGNN_DEVERR_CLASS_TARGET among them, and nothing else. */
+int hgnn_ccn_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                              const int64_t* d_n_batch, const float* d_y, float* const* params,
+                              float* const* grads, float* const* exp_avg, float* const* exp_inf,
+                              const float* d_clr, double beta1, double beta2, double eps, double weight_decay,
+                              float* d_stats, float* d_out, int32_t* d_err, int32_t tag, void* stream);
 /* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
  * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
  * as above.  One block, fp64 sums in a fixed order: the same bits every call. */
 int hgnn_ccn_eval_loss(const float* d_out, const float* d_y, int n_graphs, int n_out, double t_mean,
                        double t_std, float* d_res, void* stream);
+/* The classification branch of the same meters (test_ccn.py:40-41, 52-55): d_y (n_graphs,) class indices stored
+ * as float; d_res[0] = mean over graphs of the per-graph cross entropy (losses.avg), d_res[1] = 0 (error.avg,
+ * never updated on this branch), d_res[2] = the fraction of graphs whose first maximum (torch.argmax's tie
+ * rule) is the target.  A target that is not an integer in [0, n_out) ORs 1 into *d_err and adds to neither
+ * sum; the divisor stays n_graphs.  One block, fp64 sums in the same fixed order. */
+int hgnn_ccn_eval_xent(const float* d_out, const float* d_y, int n_graphs, int n_out, float* d_res,
+                       uint32_t* d_err, void* stream);
 
 /* collapse6to3 (functions/contraction.py:106-121) on a general 6-D tensor
  * F (C, n, n, n, n, n) -> (n, n, 18 C); the 18 contractions of _c6to2_111 /

@@ -6,7 +6,13 @@ QM9-shape graphs alternate between three paths,
   fused     CcnTrainStep(fused=True): hgnn_ccn_small_train, one dispatch per epoch
 
 each on its own copy of CCN_1D(5, 1, 2, 2).  Per path the min and median ms per graph over the epochs, printed
-as one JSON line and written to profiles/ccn_train_ab.json.  The tool holds no expectation."""
+as one JSON line and written to profiles/ccn_train_ab.json.  The tool holds no expectation.
+
+--loss xent: the classification branch (train_ccn.py:39-41, 56-57) on the generated driver's task
+(scripts/main_generate_ccn.py): three_collinear_points(256, n_max=30, seed=0) with CCN_1D(5, 2, 2, 10),
+nn.CrossEntropyLoss on out.view(1, -1), hgnn_xent_loss / hgnn_ccn_small_train_xent; written to
+profiles/ccn_train_xent_ab.json."""
+import argparse
 import copy
 import json
 import os
@@ -25,15 +31,24 @@ def main():
     import hgnn_amd.datagen as dg
     from hgnn_amd.train import CcnTrainStep
     from models.compnets.model_ccn import CCN_1D
-    graphs = dg.qm9_shape_dataset(256, seed=7)
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--loss", choices=("mse", "xent"), default="mse")
+    xent = ap.parse_args().loss == "xent"
+    if xent:
+        graphs = [(d[0], d[1], d[2].float()) for d in dg.three_collinear_points(256, n_max=30, seed=0)]
+    else:
+        graphs = dg.qm9_shape_dataset(256, seed=7)
     torch.manual_seed(0)
-    nets = {"torch": CCN_1D(5, 1, 2, 2).cuda()}
+    nets = {"torch": (CCN_1D(5, 2, 2, 10) if xent else CCN_1D(5, 1, 2, 2)).cuda()}
     nets["unfused"] = copy.deepcopy(nets["torch"])
     nets["fused"] = copy.deepcopy(nets["torch"])
     opt = torch.optim.Adamax(nets["torch"].parameters(), lr=LR)
-    crit = torch.nn.MSELoss()
-    data = [(x.cuda(), (a + torch.eye(a.shape[0])).cuda(), ((t[0].view(1) - MEAN) / (STD + 10 ** -8)).cuda())
-            for x, a, t in graphs]
+    crit = torch.nn.CrossEntropyLoss() if xent else torch.nn.MSELoss()
+    if xent:
+        data = [(x.cuda(), (a + torch.eye(a.shape[0])).cuda(), t[0].view(1).long().cuda()) for x, a, t in graphs]
+    else:
+        data = [(x.cuda(), (a + torch.eye(a.shape[0])).cuda(), ((t[0].view(1) - MEAN) / (STD + 10 ** -8)).cuda())
+                for x, a, t in graphs]
     nmax = max(x.shape[0] for x, _, _ in graphs)
     X = torch.zeros(len(graphs), nmax, 5)
     A = torch.zeros(len(graphs), nmax, nmax)
@@ -43,15 +58,16 @@ def main():
         A[b, :n, :n] = a + torch.eye(n)
     X, A = X.cuda(), A.cuda()
     nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64).cuda()
-    Y =torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
-    steps = {k: CcnTrainStep(nets[k], lr=LR, t_mean=MEAN, t_std=STD, fused=(k == "fused"))
-             for k in ("unfused", "fused")}
+    Y = torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
+    stats = dict(classification=True) if xent else dict(t_mean=MEAN, t_std=STD)
+    steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused"), **stats) for k in ("unfused", "fused")}
 
     def torch_epoch():
         net = nets["torch"]
         for x, a, y in data:
             opt.zero_grad()
-            loss = crit(net(x, a), y)
+            out = net(x, a)
+            loss = crit(out.view(1, -1) if xent else out, y)
             loss.backward()
             opt.step()
 
@@ -68,11 +84,13 @@ def main():
                 times[k].append((time.perf_counter() - t0) * 1e3 / len(graphs))
     res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5)}
            for k, v in times.items()}
+    res["loss"] = "xent" if xent else "mse"
     res["graphs"] = len(graphs)
+    res["nmax"] = nmax
     res["epochs"] = len(times["fused"])
     print(json.dumps(res))
     os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
-    with open(os.path.join(REPO, "profiles", "ccn_train_ab.json"), "w") as f:
+    with open(os.path.join(REPO, "profiles", "ccn_train_xent_ab.json" if xent else "ccn_train_ab.json"), "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
 
