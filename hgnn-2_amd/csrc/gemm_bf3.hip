@@ -197,7 +197,11 @@ __global__ void __launch_bounds__(G_NT) k_gemm_bf3_fwd(const float* __restrict__
     acc += tacc;
     // epilogue (k_gemm3 E3_FWD's): bias, ReLU, store, BN partials (count, mean, M2) per 64-row tile.
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    float* red = reinterpret_cast<float*>(lds);  // free: the main loop ended with a barrier
+    // red / redd: the stage buffer mma(nt - 1) does not read (its last reader, mma(nt - 2), is followed by the
+    // loop's barrier; unused at nt = 1) -- no barrier follows the last stage's MFMAs, so its own buffer is still
+    // being read by the slower waves
+    char* const free_st = lds + (nt & 1) * G_STAGE;
+    float* red = reinterpret_cast<float*>(free_st);
     const int col = wn * 32 + r31, gn = n0 + col;
     const float bv = gn < N ? bias[gn] : 0.f;
     const bool relu = gn >= relu_from;
@@ -225,7 +229,7 @@ __global__ void __launch_bounds__(G_NT) k_gemm_bf3_fwd(const float* __restrict__
         // no-return fp64 atomic per column and statistic into copy bx % BN_ACC_COPIES (spreads the adders)
         s1 += __shfl_xor(s1, 32, 64);
         s2 += __shfl_xor(s2, 32, 64);
-        double* redd = reinterpret_cast<double*>(lds);  // free: the main loop ended with a barrier
+        double* redd = reinterpret_cast<double*>(free_st);  // (the stage buffer the last MFMAs do not read)
         if (lane < 32 && wm == 1) {
             redd[col] = s1;
             redd[G_BN + col] = s2;

@@ -68,6 +68,29 @@ class CcnConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("order", "bs", "nmax", "f_in", "hidden", "layers", "n_out", "reserved")]
 
 
+class ProbeDiag(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "diag", "mean", "std", "w", "b")] + \
+               [(n, ctypes.c_int32) for n in ("ldx", "c")]
+
+
+class ProbeFwd(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("a", "m_valid", "wl", "wr", "bl", "br", "y", "mean", "std", "run_mean",
+                                                "run_std", "ticket_out")] + \
+               [("diag", ProbeDiag)] + \
+               [(n, ctypes.c_int32) for n in ("lda", "m_cap", "d", "k", "relu_from", "ldy", "kernel", "bn")]
+
+
+class ProbeDa(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("dy", "m_valid", "wl", "wr", "bl", "br", "da")] + \
+               [(n, ctypes.c_int32) for n in ("lddy", "m_cap", "d", "k", "ldda", "kernel")]
+
+
+class ProbeDw(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("dy", "a", "r_valid", "dbpart", "dw0", "dw1", "db0", "db1")] + \
+               [("diag", ProbeDiag)] + \
+               [(n, ctypes.c_int32) for n in ("lddy", "lda", "r_cap", "o", "o_real", "split", "k", "nz")]
+
+
 _lib = None
 
 _VP = ctypes.c_void_p
@@ -150,6 +173,12 @@ SIGNATURES = {
     "hgnn_conv1x1_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
     "hgnn_conv1x1_forward": ([_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP], _I),
     "hgnn_conv1x1_backward": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP], _I),
+    "hgnn_probe_repack": ([_VP, _VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP], _I),
+    "hgnn_probe_gemm_workspace_bytes": ([_I, _I, _I], ctypes.c_size_t),
+    "hgnn_probe_gemm_fwd": ([ctypes.POINTER(ProbeFwd), _VP, _VP], _I),
+    "hgnn_probe_gemm_da": ([ctypes.POINTER(ProbeDa), _VP, _VP], _I),
+    "hgnn_probe_dw_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
+    "hgnn_probe_gemm_dw": ([ctypes.POINTER(ProbeDw), _VP, _VP], _I),
 }
 
 

@@ -496,6 +496,92 @@ int hgnn_conv1x1_backward(const float* d_x, const float* d_w, const float* d_dy,
                           float* d_dw, float* d_db, int bs, int cin, int cout, int n,
                           void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------
+ * Kernel probes (tests and inspection).
+ *
+ * The Conv1d-pair GEMMs of the executor (csrc/gemm_bf3.hip, csrc/gemm3.hip) and the weight repack
+ * (csrc/kernels.h repack_part) behind plain entry points, so a test can hand one kernel any shape
+ * its launcher accepts.  A probe takes the pair as the executor holds it (wl, wr (d, k) row-major,
+ * bl, br (d)), runs the repack itself and passes the GEMM the repacked operands with the executor's
+ * leading dimensions: kp = k rounded up to 4, c2 = 2d, c2p = c2 rounded up to 4, bf16 plane rows of
+ * ld3(x) = x rounded up to 16.  Nothing is allocated; the caller's workspace is sized by the
+ * *_workspace_bytes query; every call only enqueues work on `stream`; the launcher's status comes
+ * back unchanged.  No switch is added: the HGNN_* switches select kernel variants as they do in
+ * the executor.
+ * ---------------------------------------------------------------------- */
+
+/* The diagonal I / D operand columns (csrc/kernels.h DiagIdArgs); x == NULL: none.  The logical
+ * operand is [v_0 z | v_1 z | A] with z = fmaf(x - mean, w / std, b) and (v_0, v_1) = diag[row]. */
+typedef struct hgnn_probe_diag {
+    const float* x;     /* [rows][ldx] */
+    const float* diag;  /* [rows][2] */
+    const float* mean;  /* (c) */
+    const float* std;   /* (c) */
+    const float* w;     /* scalar */
+    const float* b;     /* scalar */
+    int32_t ldx, c;
+} hgnn_probe_diag;
+
+/* One repack item.  Outputs: wt [k][c2p] (columns >= c2 zero), wc [c2][kp] (columns >= k zero),
+ * bc (c2), wc3 [3][c2][ld3(kp)], wt3 [3][k][ld3(c2p)] (bf16, the three split planes, zero padding). */
+int hgnn_probe_repack(const float* d_wl, const float* d_wr, const float* d_bl, const float* d_br, int d, int k,
+                      float* d_wt, float* d_wc, float* d_bc, void* d_wc3, void* d_wt3, void* stream);
+
+/* Workspace of hgnn_probe_gemm_fwd / hgnn_probe_gemm_da for a pair (d, k) and m_cap rows. */
+size_t hgnn_probe_gemm_workspace_bytes(int d, int k, int m_cap);
+
+typedef struct hgnn_probe_fwd {
+    const float* a;          /* [m_cap][lda]: the aggregate (k - 2c columns used with diag, else k) */
+    const int32_t* m_valid;  /* device row count, or NULL: m_cap */
+    const float* wl;
+    const float* wr;
+    const float* bl;
+    const float* br;
+    float* y;                /* [m_cap][ldy], 2d columns written */
+    float* mean;             /* bn != 0: (2d) */
+    float* std;
+    float* run_mean;         /* optional, read and updated in place (momentum 0.1) */
+    float* run_std;
+    uint32_t* ticket_out;    /* bn == 3, optional: the ticket's value after the launch */
+    hgnn_probe_diag diag;
+    int32_t lda, m_cap, d, k, relu_from, ldy;
+    int32_t kernel;          /* 0: split-bf16; 1: fp32 (mfma16 = 0); 2: fp32 (mfma16 = 1) */
+    int32_t bn;              /* 0: none; 1: per-tile partials + finalize; 2: fp64 sums + finalize;
+                                3: fp64 sums, the finalize in the GEMM's last block (2, 3: kernel 0 only) */
+} hgnn_probe_fwd;
+int hgnn_probe_gemm_fwd(const hgnn_probe_fwd* p, void* workspace, void* stream);
+
+/* dA [m_cap][ldda] (k columns written) = dY [m_cap][lddy] (c2p columns read) . Wcat. */
+typedef struct hgnn_probe_da {
+    const float* dy;
+    const int32_t* m_valid;
+    const float* wl;
+    const float* wr;
+    const float* bl;
+    const float* br;
+    float* da;
+    int32_t lddy, m_cap, d, k, ldda;
+    int32_t kernel;          /* 0: split-bf16; 1: fp32 */
+} hgnn_probe_da;
+int hgnn_probe_gemm_da(const hgnn_probe_da* p, void* workspace, void* stream);
+
+/* The dW GEMM and its slab reduction.  nz = 0: dw3_chunks(r_cap, o, k).  The workspace holds only
+ * the nz split-K slabs [nz][o][k], from its first byte. */
+size_t hgnn_probe_dw_workspace_bytes(int r_cap, int o, int k, int nz);
+typedef struct hgnn_probe_dw {
+    const float* dy;         /* [r_cap][lddy], o columns read */
+    const float* a;          /* [r_cap][lda]: the saved operand (k - 2c columns with diag, else k) */
+    const int32_t* r_valid;  /* device row count (required) */
+    const float* dbpart;     /* optional [ceil(r_cap / 64)][o_real]: per-tile column sums of dY */
+    float* dw0;              /* [split][k] */
+    float* dw1;              /* [o_real - split][k] */
+    float* db0;              /* with dbpart: (split) */
+    float* db1;              /* with dbpart: (o_real - split) */
+    hgnn_probe_diag diag;
+    int32_t lddy, lda, r_cap, o, o_real, split, k, nz;
+} hgnn_probe_dw;
+int hgnn_probe_gemm_dw(const hgnn_probe_dw* p, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
