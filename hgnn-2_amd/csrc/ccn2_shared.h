@@ -9,8 +9,18 @@ namespace {
 
 enum { WA, WB, WQ1, WQ2, WQ3, WQ4, WQ15, WQ16, WQ17, NWC };
 
+// A global word read where the block may have written it earlier in the same dispatch (the training loop of
+// ccn2_small.hip: the weights after an optimizer step, the readout features): FR makes the read an agent-scope
+// load, which stays on the vector path -- the scalar cache is not coherent with the block's own stores.  Without
+// FR it is the plain load the one-shot kernels have always had.
+template <bool FR>
+__device__ __forceinline__ float c2_ld(const float* p) {
+    if constexpr (FR) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+
 // combined weights of output channels [o0, o0 + hc): wc[k][o][c]
-template <int HC, int CM>
+template <int HC, int CM, bool FR = false>
 __device__ __forceinline__ void c2_weights(float (*wc)[HC][CM], const float* __restrict__ W, int cin, int o0, int hc) {
     const int K = 18 * cin;
     for (int t = threadIdx.x; t < HC * CM; t += blockDim.x) {
@@ -19,7 +29,10 @@ __device__ __forceinline__ void c2_weights(float (*wc)[HC][CM], const float* __r
         const float* w = W + (long long)(o0 + (ok ? o : 0)) * K;
         float r[18];
 #pragma unroll
-        for (int q = 0; q < 18; ++q) r[q] = ok ? w[q * cin + c] : 0.f;
+        for (int q = 0; q < 18; ++q) {
+            if constexpr (FR) r[q] = ok ? c2_ld<true>(w + q * cin + c) : 0.f;
+            else r[q] = ok ? w[q * cin + c] : 0.f;
+        }
         float a = r[0];
 #pragma unroll
         for (int q = 6; q < 15; ++q) a += r[q];

@@ -505,7 +505,7 @@ int launch_dw_readout(const DwDenseArgs& a, hipStream_t s);
 // ---------------------------------------------------------------- optimizer
 // One element of torch.optim.Adamax in torch's operation order (train.hip): g += wd p; m = lerp(m, g, w) with
 // w = 1 - beta1 < 0.5; u = max(beta2 u, |g| + eps); p -= lr_c m / u with lr_c = lr / (1 - beta1^t).  The one
-// definition of the update: k_adamax and the CCN training kernel (ccn_small.hip) both inline it.
+// definition of the update: k_adamax and the CCN training kernels (ccn_small.hip, ccn2_small_train.hip) all inline it.
 __device__ __forceinline__ void adamax_elem(float& p, float g, float& m, float& u, float lr_c, float w, float beta2,
                                             float eps, float wd) {
     if (wd != 0.f) g = g + wd * p;
@@ -526,7 +526,7 @@ __device__ __forceinline__ bool xent_target(float y, int c, int& ti) {
 // The row's loss logsumexp(x) - x[ti] in a serial order over the classes (max, sum of expf(x - max), lse = max +
 // logf(sum)) and, when dout is given, dout[k] = (softmax(x)[k] - onehot(ti)[k]) * inv.  dout may be x itself:
 // x[ti] is read first and element k is written after its last read.  The one definition of the row: k_xent_loss,
-// k_ccn_eval_xent and the CCN training kernel (ccn_small.hip) all inline it.
+// k_ccn_eval_xent and the CCN training kernels (ccn_small.hip, ccn2_small_train.hip) all inline it.
 __device__ __forceinline__ float xent_row(const float* x, int ti, int c, float inv, float* dout) {
     float m = x[0];
     for (int k = 1; k < c; ++k) m = fmaxf(m, x[k]);

@@ -178,7 +178,13 @@ class TrainStep:
         self._targets.check()
 
 
-CCN_TRAIN_MAX_GRAPHS = 4096  # csrc/ccn_small.hip CS_TRAIN_GMAX: graphs per hgnn_ccn_small_train dispatch
+# graphs per hgnn_ccn_small_train / hgnn_ccn2_small_train dispatch (csrc/ccn_small.hip CS_TRAIN_GMAX,
+# csrc/ccn2_small.hip Q_TRAIN_GMAX)
+CCN_TRAIN_MAX_GRAPHS = 4096
+# Whether fused=None takes hgnn_ccn2_small_train for CCN_2D.  Decided by the same-process A/B of
+# tools/ab_ccn_train.py --order 2 ("The CCN-2D loop without the host"): the kernel's median per graph
+# against the unfused loop's.
+CCN2_TRAIN_FUSED_DEFAULT = True
 
 
 class CcnTrainStep:
@@ -191,12 +197,17 @@ class CcnTrainStep:
 
       fused    hgnn_ccn_small_train: one dispatch for the whole list (CCN_1D within the small-graph bounds:
                graphs of <= 64 nodes, input_feats and hidden_size <= 8)
+      fused2d  hgnn_ccn2_small_train: the same for CCN_2D (graphs of <= 32 nodes, input_feats <= 8,
+               hidden_size <= 2, n_outputs <= 256); its one-graph workspace is allocated once per nmax and kept
       unfused  per graph forward_batch on the one-graph slice, hgnn_mse_loss, autograd backward and
-               hgnn_adamax_step: the same arithmetic from the separate entry points (CCN_2D, larger graphs,
-               wider channels)
+               hgnn_adamax_step: the same arithmetic from the separate entry points (larger graphs, wider
+               channels)
 
-    fused=None takes the fused kernel wherever hgnn_ccn_small_train_supported allows it, fused=False never,
-    fused=True raises where it is not supported.  Neither path synchronises with the host.
+    fused=None takes a fused kernel wherever hgnn_ccn_small_train_supported or hgnn_ccn2_small_train_supported
+    allows it (the latter by CCN2_TRAIN_FUSED_DEFAULT, the measured default), fused=False never; fused=True means
+    the CCN_1D kernel and raises where that is not supported (so for every CCN_2D model), fused="ccn2" means the
+    CCN_2D kernel and raises likewise.  After each step, .path says which of the three ran.  No path synchronises
+    with the host.
 
     A graph the fused kernel rejects (missing self loop, asymmetric pattern, n_b outside [0, nmax]) takes no
     step and updates no meter; the error shows at the next check (hgnn_amd.net.check_errors(), or at once
@@ -205,11 +216,11 @@ class CcnTrainStep:
     Classification (the reference's `mean == 0` branch, train_ccn.py:39-41, 56-57, the generated-data driver
     scripts/main_generate_ccn.py): classification=True, or classification=None with t_mean == 0.0 as in
     TrainStep.  y then holds one class index per graph, the loss is nn.CrossEntropyLoss on the graph's output
-    viewed as (1, n_outputs), and the MAE meters stats[1] and stats[3] are never written.  The fused path is
-    hgnn_ccn_small_train_xent, the unfused path uses hgnn_xent_loss with n = 1.  A target that is not an
+    viewed as (1, n_outputs), and the MAE meters stats[1] and stats[3] are never written.  The fused paths are
+    hgnn_ccn_small_train_xent and hgnn_ccn2_small_train_xent, the unfused path uses hgnn_xent_loss with n = 1.  A target that is not an
     integer in [0, n_outputs) raises the class-target error at the next check (the next step,
     check_targets(), or at once under HGNN_STRICT=1) on both paths, which otherwise differ on such a graph:
-    the fused kernel skips it like a rejected graph (no step), the unfused path does what TrainStep does (the
+    a fused kernel skips it like a rejected graph (no step), the unfused path does what TrainStep does (the
     row's dout is zero and the Adamax step is still taken, on zero gradients).
 
     fused=None and classification: the kernel's backward LDS layout bounds the graph size by the depth (at the
@@ -248,11 +259,19 @@ class CcnTrainStep:
         self.t_std = float(t_std)
         self.spec = model._spec()
         self.fused = fused
-        if fused and not self._supported(1):
+        if isinstance(fused, str):
+            if fused != "ccn2":
+                raise RuntimeError(f"hgnn_amd: fused={fused!r}: expected None, False, True or \"ccn2\"")
+            if not self._supported2d(1):
+                raise RuntimeError("hgnn_amd: fused=\"ccn2\" needs CCN_2D with input_feats <= 8, hidden_size <= 2 "
+                                   "and n_outputs <= 256 (hgnn_ccn2_small_train_supported)")
+        elif fused and not self._supported(1):
             raise RuntimeError("hgnn_amd: fused=True needs CCN_1D with input_feats and hidden_size <= 8 "
                                "(hgnn_ccn_small_train_supported)")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
         self.out = None
+        self.path = None  # "fused", "fused2d" or "unfused": what the last step ran
+        self._ws2d = {}   # nmax -> the CCN-2D kernel's one-graph workspace
         self._grads = [torch.zeros_like(p) for p in self.params]
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
         # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
@@ -274,6 +293,29 @@ class CcnTrainStep:
     def _supported(self, nmax):
         cfg = self.spec.config(1, nmax)
         return bool(L.lib().hgnn_ccn_small_train_supported(ctypes.byref(cfg)))
+
+    def _supported2d(self, nmax):
+        cfg = self.spec.config(1, nmax)
+        return bool(L.lib().hgnn_ccn2_small_train_supported(ctypes.byref(cfg)))
+
+    def _route(self, nmax):
+        """The path of a chunk padded to nmax nodes."""
+        fused = self.fused
+        if fused is None:
+            if self._supported(nmax):
+                return "fused"
+            return "fused2d" if CCN2_TRAIN_FUSED_DEFAULT and self._supported2d(nmax) else "unfused"
+        if fused == "ccn2":
+            if not self._supported2d(nmax):
+                raise RuntimeError(f"hgnn_amd: fused=\"ccn2\", but nmax = {nmax} is outside the CCN-2D kernel's "
+                                   "bounds (hgnn_ccn2_small_train_supported)")
+            return "fused2d"
+        if fused:
+            if not self._supported(nmax):
+                raise RuntimeError(f"hgnn_amd: fused=True, but nmax = {nmax} is outside the fused kernel's bounds "
+                                   "(hgnn_ccn_small_train_supported)")
+            return "fused"
+        return "unfused"
 
     def _inputs(self, X, adj, n_batch, y):
         from .ccn import _check_shapes
@@ -300,20 +342,24 @@ class CcnTrainStep:
         self._targets.poll(block=False)
         X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
         G, nmax = X.shape[0], X.shape[1]
-        fused = self.fused
-        if fused is None:
-            fused = self._supported(nmax)
-        elif fused and not self._supported(nmax):
-            raise RuntimeError(f"hgnn_amd: fused=True, but nmax = {nmax} is outside the fused kernel's bounds "
-                               "(hgnn_ccn_small_train_supported)")
+        self.path = path = self._route(nmax)  # before the work: a strict check inside it may raise
         self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
-        if fused:
-            self._step_fused(X, adj, n_batch, y)
-        else:
+        if path == "unfused":
             self._step_unfused(X, adj, n_batch, y)
+        else:
+            self._step_fused(X, adj, n_batch, y, two=path == "fused2d")
         return self.stats
 
-    def _step_fused(self, X, adj, n_batch, y):
+    def _workspace2d(self, nmax, dev):
+        ws = self._ws2d.get(nmax)
+        if ws is None:
+            cfg = self.spec.config(1, nmax)
+            ws = torch.empty(L.lib().hgnn_ccn2_small_train_workspace_bytes(ctypes.byref(cfg)), dtype=torch.uint8,
+                             device=dev)
+            self._ws2d[nmax] = ws
+        return ws
+
+    def _step_fused(self, X, adj, n_batch, y, two=False):
         from .ccn import _word
         from .net import _capturing, check_errors, strict
         lib = L.lib()
@@ -321,6 +367,10 @@ class CcnTrainStep:
         dev = X.device
         stream = L.stream_handle(dev)
         b1, b2 = self.betas
+        # order 2: the kernel's one-graph workspace goes before the error word
+        ws = (L.ptr(self._workspace2d(X.shape[1], dev)),) if two else ()
+        name = ("hgnn_ccn2_small_train" if two else "hgnn_ccn_small_train") + ("_xent" if self.classification else "")
+        entry = getattr(lib, name)
         for g0 in range(0, X.shape[0], CCN_TRAIN_MAX_GRAPHS):
             g1 = min(g0 + CCN_TRAIN_MAX_GRAPHS, X.shape[0])
             cfg = self.spec.config(g1 - g0, X.shape[1])
@@ -334,11 +384,11 @@ class CcnTrainStep:
                     L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]))
             tail = (L.ptr_array(self.params), L.ptr_array(self._grads), L.ptr_array(self.exp_avg),
                     L.ptr_array(self.exp_inf), L.ptr(clr), b1, b2, self.eps, self.weight_decay, L.ptr(self.stats),
-                    L.ptr(self.out[g0:g1]), err, tag, stream)
+                    L.ptr(self.out[g0:g1]), *ws, err, tag, stream)
             if self.classification:
-                L.check(lib.hgnn_ccn_small_train_xent(*head, *tail), "hgnn_ccn_small_train_xent")
+                L.check(entry(*head, *tail), name)
             else:
-                L.check(lib.hgnn_ccn_small_train(*head, self.t_mean, self.t_std, *tail), "hgnn_ccn_small_train")
+                L.check(entry(*head, self.t_mean, self.t_std, *tail), name)
             self.step_count += g1 - g0
         for p, g in zip(self.params, self._grads):
             p.grad = g

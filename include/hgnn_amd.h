@@ -421,6 +421,36 @@ int hgnn_ccn_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, cons
                               float* const* grads, float* const* exp_avg, float* const* exp_inf,
                               const float* d_clr, double beta1, double beta2, double eps, double weight_decay,
                               float* d_stats, float* d_out, int32_t* d_err, int32_t tag, void* stream);
+/* The same per-graph loop for CCN_2D (the drivers' other model: scripts/main_ccn_qm9.py:140,145) in ONE dispatch:
+ * one 512-thread workgroup walks the cfg->bs graphs in index order.  Per graph the arithmetic is that of
+ * hgnn_ccn_small_forward / _backward (order 2) on the one-graph slice, hgnn_mse_loss (or hgnn_xent_loss with
+ * n = 1) and hgnn_adamax_step, bit for bit: out, every gradient, both moments and the parameters.  (The running
+ * loss of the _xent entry may differ from hgnn_xent_loss's in its last bit, as for order 1.)  No dX is formed.
+ *   supported: host only; 1 for order 2 with nmax <= 32, f_in <= 8, hidden <= 2, layers <= 15,
+ *     f_in + layers * hidden <= 64 and n_out <= 256 (the graph's out / dout row is a 1 KB static LDS buffer), the
+ *     kernel's LDS -- hgnn_ccn_small_supported's order-2 carve plus that 1 KB -- within 160 KB (nmax = 32 uses
+ *     about 140 KB); cfg->bs is not looked at.  Else 0.
+ *   workspace_bytes: one graph's region whatever cfg->bs is -- the (L + 2) nmax^3 hidden floats of the levels
+ *     and the dp format, the per-node parameter partials and a feature row -- reused by every graph of the
+ *     dispatch; 0 where unsupported.  The caller may keep it across calls; nothing in it is read before it is
+ *     written.
+ *   Arguments, the rejected graphs (validation bits; _xent: a class target that is no integer in [0, n_out)) and
+ *     the return codes are those of hgnn_ccn_small_train / _xent, with the workspace before d_err.
+ *     hgnn_ccn_small_train* itself keeps returning HGNN_ERR_UNSUPPORTED for order 2. */
+int hgnn_ccn2_small_train_supported(const hgnn_ccn_config* cfg);
+size_t hgnn_ccn2_small_train_workspace_bytes(const hgnn_ccn_config* cfg);
+int hgnn_ccn2_small_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                          const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                          float* const* params, float* const* grads, float* const* exp_avg,
+                          float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
+                          double weight_decay, float* d_stats, float* d_out, void* workspace, int32_t* d_err,
+                          int32_t tag, void* stream);
+int hgnn_ccn2_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                               const int64_t* d_n_batch, const float* d_y, float* const* params,
+                               float* const* grads, float* const* exp_avg, float* const* exp_inf,
+                               const float* d_clr, double beta1, double beta2, double eps, double weight_decay,
+                               float* d_stats, float* d_out, void* workspace, int32_t* d_err, int32_t tag,
+                               void* stream);
 /* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
  * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
  * as above.  One block, fp64 sums in a fixed order: the same bits every call. */

@@ -1,4 +1,4 @@
-"""Same-process A/B of the per-graph CCN-1D training loop (scripts/train_ccn.py:31-73): epochs over the same 256
+"""Same-process A/B of the per-graph CCN training loop (scripts/train_ccn.py:31-73): epochs over the same 256
 QM9-shape graphs alternate between three paths,
 
   torch     net(x, a), nn.MSELoss, torch.optim.Adamax per graph (the drop-in model under the reference's loop)
@@ -11,7 +11,11 @@ as one JSON line and written to profiles/ccn_train_ab.json.  The tool holds no e
 --loss xent: the classification branch (train_ccn.py:39-41, 56-57) on the generated driver's task
 (scripts/main_generate_ccn.py): three_collinear_points(256, n_max=30, seed=0) with CCN_1D(5, 2, 2, 10),
 nn.CrossEntropyLoss on out.view(1, -1), hgnn_xent_loss / hgnn_ccn_small_train_xent; written to
-profiles/ccn_train_xent_ab.json."""
+profiles/ccn_train_xent_ab.json.
+
+--order 2: the same three paths for CCN_2D(5, 1, 2, 2) on the same 256 QM9-shape graphs, the fused path being
+CcnTrainStep(fused="ccn2"): hgnn_ccn2_small_train; written to profiles/ccn2_train_ab.json.  With --loss xent:
+CCN_2D(5, 2, 2, 2) on those graphs with the label g % 2, written to profiles/ccn2_train_xent_ab.json."""
 import argparse
 import copy
 import json
@@ -30,16 +34,24 @@ MEAN, STD, LR = 0.3, 1.7, 1e-3
 def main():
     import hgnn_amd.datagen as dg
     from hgnn_amd.train import CcnTrainStep
-    from models.compnets.model_ccn import CCN_1D
+    from models.compnets.model_ccn import CCN_1D, CCN_2D
     ap = argparse.ArgumentParser()
     ap.add_argument("--loss", choices=("mse", "xent"), default="mse")
-    xent = ap.parse_args().loss == "xent"
-    if xent:
+    ap.add_argument("--order", type=int, choices=(1, 2), default=1)
+    args = ap.parse_args()
+    xent, two = args.loss == "xent", args.order == 2
+    if xent and two:
+        graphs = [(x, a, torch.tensor([float(g % 2)]))
+                  for g, (x, a, _) in enumerate(dg.qm9_shape_dataset(256, seed=7))]
+    elif xent:
         graphs = [(d[0], d[1], d[2].float()) for d in dg.three_collinear_points(256, n_max=30, seed=0)]
     else:
         graphs = dg.qm9_shape_dataset(256, seed=7)
     torch.manual_seed(0)
-    nets = {"torch": (CCN_1D(5, 2, 2, 10) if xent else CCN_1D(5, 1, 2, 2)).cuda()}
+    if two:
+        nets = {"torch": (CCN_2D(5, 2, 2, 2) if xent else CCN_2D(5, 1, 2, 2)).cuda()}
+    else:
+        nets = {"torch": (CCN_1D(5, 2, 2, 10) if xent else CCN_1D(5, 1, 2, 2)).cuda()}
     nets["unfused"] = copy.deepcopy(nets["torch"])
     nets["fused"] = copy.deepcopy(nets["torch"])
     opt = torch.optim.Adamax(nets["torch"].parameters(), lr=LR)
@@ -60,7 +72,7 @@ def main():
     nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64).cuda()
     Y = torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
     stats = dict(classification=True) if xent else dict(t_mean=MEAN, t_std=STD)
-    steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused"), **stats) for k in ("unfused", "fused")}
+    steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused") and ("ccn2" if two else True), **stats) for k in ("unfused", "fused")}
 
     def torch_epoch():
         net = nets["torch"]
@@ -85,12 +97,15 @@ def main():
     res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5)}
            for k, v in times.items()}
     res["loss"] = "xent" if xent else "mse"
+    res["order"] = args.order
+    res["fused_path"] = steps["fused"].path
     res["graphs"] = len(graphs)
     res["nmax"] = nmax
     res["epochs"] = len(times["fused"])
     print(json.dumps(res))
     os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
-    with open(os.path.join(REPO, "profiles", "ccn_train_xent_ab.json" if xent else "ccn_train_ab.json"), "w") as f:
+    name = ("ccn2_train" if two else "ccn_train") + ("_xent_ab.json" if xent else "_ab.json")
+    with open(os.path.join(REPO, "profiles", name), "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
 
