@@ -5,7 +5,7 @@ namespace hgnn {
 namespace {
 
 // The per-graph training loop of scripts/train_ccn.py:31-73 in one dispatch, as k_ccn1_small_train (ccn_small.hip)
-// does it for CCN-1D: ONE workgroup runs plan, forward, loss, backward and the Adamax step of graph 0, then of
+// does it for CCN-1D: ONE workgroup runs plan, forward, loss, backward and the optimizer step of graph 0, then of
 // graph 1 on the weights graph 0 left, ...  The pieces are k_ccn2_small_fwd's and k_ccn2_small_bwd's bodies (the
 // bs == 1 form: gradients written and reduced in the kernel), k_mse_loss's / xent_row's loss and adamax_elem.
 // One graph region and one graph's ppart rows serve every graph (q_plan<true>: packed base 0); the readout
@@ -24,20 +24,24 @@ constexpr size_t Q_TRAIN_STATIC = 4 * Q_OMAX + 8 * 8 + 64;  // sout, sred, sbad 
 
 struct QTrain {
     const float* y;       // (G, n_out) raw targets; XENT: (G,) class indices stored as float
-    const float* clr;     // (G,) lr / (1 - beta1^t) of the dispatch's k-th applied step
+    const float* clr;     // the scalars of the dispatch's k-th applied step at clr[k * cstride] (and + 1: Adam's
+                          // second)
     float t_mean, t_div;  // yn = (y - mean) / div, div = std + 1e-8
-    float w, beta2, eps, wd;  // w = 1 - beta1
+    OptScalars h;         // the optimizer's fixed scalars (kernels.h)
     float* p[Q_TMAX];     // parameters, gradients (QArgs' gW / gB / gfcw / gfcb alias them) and optimizer state
     float* gr[Q_TMAX];
     float* m[Q_TMAX];
-    float* u[Q_TMAX];
+    float* u[Q_TMAX];     // SGD: not touched
     int numel[Q_TMAX];
     int nt;
     float* stats;         // [4] loss, mae and their RunningAverages
     int G;
+    int cstride;          // 1: clr is (G,) lr / (1 - beta1^t); 2: the (G, 2) rows of hgnn_ccn2_small_train_opt
 };
 
-template <int CF, bool XENT>
+// OPT: the optimizer of stage 5 (HGNN_OPT_*), a template parameter like XENT, so the Adamax instantiations keep
+// their instructions.
+template <int CF, bool XENT, int OPT>
 __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
@@ -235,23 +239,20 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
             dcur = dnext;
             dnext = x;
         }
-        // 5. Adamax over every parameter element, on the gradients other waves have just written: a tensor per
-        // wave (tensors wv, wv + 8, ...), 64 elements at a time
+        // 5. the optimizer over every parameter element, on the gradients other waves have just written: a tensor
+        // per wave (tensors wv, wv + 8, ...), 64 elements at a time
         __threadfence();
         __syncthreads();
-        const float clr = t.clr[applied++];
+        const float* sc = t.clr + (long long)applied++ * t.cstride;
+        const float clr = sc[0];
+        float c1 = 0.f;
+        if constexpr (OPT == HGNN_OPT_ADAM) c1 = sc[1];
         for (int k = uniform(wv); k < t.nt; k += Q_NW) {
             float* pk = t.p[k];
             float* mk = t.m[k];
             float* uk = t.u[k];
             const float* gk = t.gr[k];
-            for (int q = lane; q < t.numel[k]; q += 64) {
-                float p = pk[q], m = mk[q], u = uk[q];
-                adamax_elem(p, gk[q], m, u, clr, t.w, t.beta2, t.eps, t.wd);
-                mk[q] = m;
-                uk[q] = u;
-                pk[q] = p;
-            }
+            for (int q = lane; q < t.numel[k]; q += 64) optim_at<OPT>(pk, gk[q], mk, uk, q, clr, c1, t.h);
         }
         // 6. the new weights visible to the next graph's reads
         __threadfence();
@@ -271,22 +272,25 @@ bool q_train_ok(const hgnn_ccn_config* c, hgnn_ccn_config& one) {
     return ccn2_small_ok(&one) && one.n_out <= Q_OMAX && q_lds_bytes(one.nmax) + Q_TRAIN_STATIC <= Q_LDS_MAX;
 }
 
-// Both training entries: the argument checks and the launch; XENT picks the loss stage (and ignores the target
-// statistics).
-template <bool XENT>
+// Every training entry: the argument checks and the launch; XENT picks the loss stage (and ignores the target
+// statistics), OPT the optimizer stage; cstride is the row length of d_clr (1: the Adamax entries' step sizes, 2:
+// the _opt entry's per-step pairs).
+template <bool XENT, int OPT>
 int q_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
             const float* d_y, double t_mean, double t_std, float* const* params, float* const* grads,
-            float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
-            double weight_decay, float* d_stats, float* d_out, void* d_ws, int32_t* d_err, int32_t tag, void* stream) {
+            float* const* exp_avg, float* const* exp_inf, const float* d_clr, int cstride, double beta1, double beta2,
+            double eps, double weight_decay, float* d_stats, float* d_out, void* d_ws, int32_t* d_err, int32_t tag,
+            void* stream) {
+    constexpr bool TWO = OPT != HGNN_OPT_SGD;  // whether the second state array is used
     hgnn_ccn_config one;
     if (!q_train_ok(cfg, one)) return HGNN_ERR_UNSUPPORTED;
-    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || !exp_inf || !d_clr || !d_stats || !d_out ||
-        !d_ws || !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > Q_TRAIN_GMAX ||
+    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || (TWO && !exp_inf) || !d_clr || !d_stats ||
+        !d_out || !d_ws || !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > Q_TRAIN_GMAX ||
         (XENT && cfg->n_out < 2))
         return HGNN_ERR_ARG;
     const int nt = 2 * cfg->layers + 2;
     for (int k = 0; k < nt; ++k)
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_inf[k]) return HGNN_ERR_ARG;
+        if (!params[k] || !grads[k] || !exp_avg[k] || (TWO && !exp_inf[k])) return HGNN_ERR_ARG;
     // the one-graph layout of the workspace and of the backward (gradients written directly); the kernel reads
     // graph g's data at index g
     QArgs a = q_args(&one, d_X, d_adj, d_n_batch, params, d_ws);
@@ -302,19 +306,17 @@ int q_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, co
     QTrain t{};
     t.y = d_y;
     t.clr = d_clr;
+    t.cstride = cstride;
     // scalars combine in double and reach the kernel as fp32, as the reference's Python floats reach torch
     t.t_mean = (float)t_mean;
     t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
-    t.w = (float)(1.0 - beta1);
-    t.beta2 = (float)beta2;
-    t.eps = (float)eps;
-    t.wd = (float)weight_decay;
+    t.h = opt_scalars(OPT, beta1, beta2, eps, weight_decay);
     const int nf = q_nf(cfg);
     for (int k = 0; k < nt; ++k) {
         t.p[k] = params[k];
         t.gr[k] = grads[k];
         t.m[k] = exp_avg[k];
-        t.u[k] = exp_inf[k];
+        t.u[k] = TWO ? exp_inf[k] : nullptr;
         const int l = k / 2;
         if (l < cfg->layers) t.numel[k] = k % 2 ? cfg->hidden : cfg->hidden * 18 * (l == 0 ? cfg->f_in : cfg->hidden);
         else t.numel[k] = k % 2 ? cfg->n_out : cfg->n_out * nf;
@@ -324,12 +326,12 @@ int q_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, co
     t.G = cfg->bs;
     static bool attr = false;
     if (!attr) {  // the kernel's static LDS counts against the same cap
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ccn2_small_train<Q_CF, XENT>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ccn2_small_train<Q_CF, XENT, OPT>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(Q_LDS_MAX - Q_TRAIN_STATIC));
         (void)hipGetLastError();  // a refused opt-in shows at the launch, not here
         attr = true;
     }
-    HGNN_KLAUNCH((k_ccn2_small_train<Q_CF, XENT>), dim3(1), dim3(Q_NT), q_lds_bytes(one.nmax), (hipStream_t)stream, a,
+    HGNN_KLAUNCH((k_ccn2_small_train<Q_CF, XENT, OPT>), dim3(1), dim3(Q_NT), q_lds_bytes(one.nmax), (hipStream_t)stream, a,
                  t);
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
@@ -357,8 +359,9 @@ int hgnn_ccn2_small_train(const hgnn_ccn_config* cfg, const float* d_X, const fl
                           float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
                           double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
                           void* workspace, int32_t* d_err, int32_t tag, void* stream) {
-    return q_train<false>(cfg, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, grads, exp_avg, exp_inf, d_clr,
-                          beta1, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err, tag, stream);
+    return q_train<false, HGNN_OPT_ADAMAX>(cfg, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, grads, exp_avg,
+                                           exp_inf, d_clr, 1, beta1, beta2, eps, weight_decay, d_stats, d_out,
+                                           workspace, d_err, tag, stream);
 }
 
 int hgnn_ccn2_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
@@ -366,8 +369,30 @@ int hgnn_ccn2_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, con
                                float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
                                double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
                                void* workspace, int32_t* d_err, int32_t tag, void* stream) {
-    return q_train<true>(cfg, d_X, d_adj, d_n_batch, d_y, 0.0, 1.0, params, grads, exp_avg, exp_inf, d_clr, beta1,
-                         beta2, eps, weight_decay, d_stats, d_out, workspace, d_err, tag, stream);
+    return q_train<true, HGNN_OPT_ADAMAX>(cfg, d_X, d_adj, d_n_batch, d_y, 0.0, 1.0, params, grads, exp_avg, exp_inf,
+                                          d_clr, 1, beta1, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err,
+                                          tag, stream);
+}
+
+int hgnn_ccn2_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,
+                              const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                              float* const* params, float* const* grads, float* const* state1, float* const* state2,
+                              const float* d_steps, double beta1_or_momentum, double beta2, double eps,
+                              double weight_decay, float* d_stats, float* d_out, void* workspace, int32_t* d_err,
+                              int32_t tag, void* stream) {
+    hgnn_ccn_config one;
+    if (!q_train_ok(cfg, one)) return HGNN_ERR_UNSUPPORTED;
+#define Q_TRAIN_OPT(X, O)                                                                                          \
+    q_train<X, O>(cfg, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, state2, \
+                  d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err, tag,  \
+                  stream)
+    switch (kind) {
+        case HGNN_OPT_ADAMAX: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_ADAMAX) : Q_TRAIN_OPT(false, HGNN_OPT_ADAMAX);
+        case HGNN_OPT_SGD: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_SGD) : Q_TRAIN_OPT(false, HGNN_OPT_SGD);
+        case HGNN_OPT_ADAM: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_ADAM) : Q_TRAIN_OPT(false, HGNN_OPT_ADAM);
+        default: return HGNN_ERR_ARG;
+    }
+#undef Q_TRAIN_OPT
 }
 
 }  // extern "C"

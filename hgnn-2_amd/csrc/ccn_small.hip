@@ -622,23 +622,25 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_bwd(CsArgs a) {
 // The per-graph training loop of scripts/train_ccn.py:31-73 in one dispatch: one workgroup runs forward, loss,
 // backward and the Adamax step of graph 0, then of graph 1, ... (per-graph SGD is sequential: graph g + 1 reads
 // the weights graph g wrote).  The pieces are the forward's and the backward's (cs_* above, the one-graph form:
-// CsArgs::bs = 1), k_mse_loss's loss and meters and k_adamax's element update (adamax_elem).
+// CsArgs::bs = 1), k_mse_loss's loss and meters and k_optim's element update (adamax_elem, sgd_elem or adam_elem).
 constexpr int CS_TMAX = 2 * CS_LMAX + 2;    // parameter tensors: level weights and biases, fc weight and bias
 constexpr int CS_TRAIN_GMAX = 4096;         // graphs per dispatch
 constexpr int CS_OMAX = CS_NW * CS_PMAX;    // n_out bound: out / dout of the graph live in CsLds::red
 
 struct CsTrain {
     const float* y;       // (G, n_out) raw targets
-    const float* clr;     // (G,) lr / (1 - beta1^t) of the dispatch's k-th applied step (a rejected graph takes none)
+    const float* clr;     // the scalars of the dispatch's k-th applied step at clr[k * cstride] (and + 1: Adam's
+                          // second); a rejected graph takes none
     float t_mean, t_div;  // yn = (y - mean) / div, div = std + 1e-8
-    float w, beta2, eps, wd;  // w = 1 - beta1
+    OptScalars h;         // the optimizer's fixed scalars (kernels.h)
     // the parameters (mutable: CsArgs' W / B / fcw / fcb alias them; none of these is const __restrict__, so
     // the re-staging of the next graph reads them by vector loads, after the fence) and the optimizer state
     float* p[CS_TMAX];
     float* m[CS_TMAX];
-    float* u[CS_TMAX];
+    float* u[CS_TMAX];    // SGD: not touched
     float* stats;         // [4] loss, mae and their RunningAverages
     int G;
+    int cstride;          // 1: clr is (G,) lr / (1 - beta1^t); 2: the (G, 2) rows of hgnn_ccn_small_train_opt
 };
 
 // a word this block wrote earlier in the dispatch, read at a wave-uniform address: an agent-scope load keeps it
@@ -650,7 +652,9 @@ __device__ __forceinline__ float cs_fresh(const float* p) {
 // XENT: the reference's `mean == 0` branch (train_ccn.py:39-41, 56-57) -- y[g] is a class index, the loss is
 // nn.CrossEntropyLoss on the graph's row (xent_row, k_xent_loss's arithmetic with n = 1) and the MAE meters are
 // never written.  A template parameter, so the MSE instantiations keep their instructions.
-template <int CF, int CH, bool XENT>
+// OPT: the optimizer of stage 5 (HGNN_OPT_*), a template parameter for the same reason: the Adamax instantiations
+// keep theirs.
+template <int CF, int CH, bool XENT, int OPT>
 __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
@@ -779,11 +783,14 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t)
             dFc = dFn;
             dFn = x;
         }
-        // 5. Adamax over every parameter element (flat: the levels in Ws' order, then fc weight and bias), on the
-        // gradients other threads have just written
+        // 5. the optimizer over every parameter element (flat: the levels in Ws' order, then fc weight and bias), on
+        // the gradients other threads have just written
         __threadfence();
         __syncthreads();
-        const float clr = t.clr[applied++];
+        const float* sc = t.clr + (long long)applied++ * t.cstride;
+        const float clr = sc[0];
+        float c1 = 0.f;
+        if constexpr (OPT == HGNN_OPT_ADAM) c1 = sc[1];
         for (int e = threadIdx.x; e < ntot; e += CS_NT) {
             int ti, q;
             const float* gp;
@@ -805,11 +812,7 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgs a, CsTrain t)
                 gp = a.gfcb;
                 q = e - nw - n_out * nf;
             }
-            float p = t.p[ti][q], m = t.m[ti][q], u = t.u[ti][q];
-            adamax_elem(p, gp[q], m, u, clr, t.w, t.beta2, t.eps, t.wd);
-            t.m[ti][q] = m;
-            t.u[ti][q] = u;
-            t.p[ti][q] = p;
+            optim_at<OPT>(t.p[ti], gp[q], t.m[ti], t.u[ti], q, clr, c1, t.h);
         }
         // 6. the new weights visible to the next graph's staging
         __threadfence();
@@ -902,20 +905,24 @@ using namespace hgnn;
 
 namespace {
 
-// Both training entries: the argument checks and the launch; XENT picks the loss stage (and ignores the target
-// statistics).
-template <bool XENT>
+// Every training entry: the argument checks and the launch; XENT picks the loss stage (and ignores the target
+// statistics), OPT the optimizer stage; cstride is the row length of d_clr (1: the Adamax entries' step sizes, 2:
+// the _opt entry's per-step pairs).
+template <bool XENT, int OPT>
 int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
              const float* d_y, double t_mean, double t_std, float* const* params, float* const* grads,
-             float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1, double beta2, double eps,
-             double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag, void* stream) {
+             float* const* exp_avg, float* const* exp_inf, const float* d_clr, int cstride, double beta1,
+             double beta2, double eps, double weight_decay, float* d_stats, float* d_out, int32_t* d_err,
+             int32_t tag, void* stream) {
+    constexpr bool TWO = OPT != HGNN_OPT_SGD;  // whether the second state array is used
     if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
-    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || !exp_inf || !d_clr || !d_stats || !d_out ||
-        !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > CS_TRAIN_GMAX || (XENT && cfg->n_out < 2))
+    if (!d_X || !d_adj || !d_y || !params || !grads || !exp_avg || (TWO && !exp_inf) || !d_clr || !d_stats ||
+        !d_out || !d_err || tag <= 0 || tag >= (1 << 23) || cfg->bs < 1 || cfg->bs > CS_TRAIN_GMAX ||
+        (XENT && cfg->n_out < 2))
         return HGNN_ERR_ARG;
     const int nt = 2 * cfg->layers + 2;
     for (int k = 0; k < nt; ++k)
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_inf[k]) return HGNN_ERR_ARG;
+        if (!params[k] || !grads[k] || !exp_avg[k] || (TWO && !exp_inf[k])) return HGNN_ERR_ARG;
     CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, nullptr);
     a.bs = 1;  // the one-graph form of the backward: gradients written directly; the kernel passes b = g
     a.out = d_out;
@@ -930,17 +937,15 @@ int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, c
     CsTrain t{};
     t.y = d_y;
     t.clr = d_clr;
+    t.cstride = cstride;
     // scalars combine in double and reach the kernel as fp32, as the reference's Python floats reach torch
     t.t_mean = (float)t_mean;
     t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
-    t.w = (float)(1.0 - beta1);
-    t.beta2 = (float)beta2;
-    t.eps = (float)eps;
-    t.wd = (float)weight_decay;
+    t.h = opt_scalars(OPT, beta1, beta2, eps, weight_decay);
     for (int k = 0; k < nt; ++k) {
         t.p[k] = params[k];
         t.m[k] = exp_avg[k];
-        t.u[k] = exp_inf[k];
+        t.u[k] = TWO ? exp_inf[k] : nullptr;
     }
     t.stats = d_stats;
     t.G = cfg->bs;
@@ -948,12 +953,12 @@ int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, c
     hipStream_t s = (hipStream_t)stream;
     if (cfg->hidden <= 2) {
         static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2, XENT>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2, XENT>), dim3(1), dim3(CS_NT), lds, s, a, t);
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2, XENT, OPT>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2, XENT, OPT>), dim3(1), dim3(CS_NT), lds, s, a, t);
     } else {
         static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF, XENT>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF, XENT>), dim3(1), dim3(CS_NT), lds, s, a, t);
+        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF, XENT, OPT>, attr);
+        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF, XENT, OPT>), dim3(1), dim3(CS_NT), lds, s, a, t);
     }
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
@@ -1079,8 +1084,9 @@ int hgnn_ccn_small_train(const hgnn_ccn_config* cfg, const float* d_X, const flo
                          float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
                          double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
                          int32_t* d_err, int32_t tag, void* stream) {
-    return cs_train<false>(cfg, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, grads, exp_avg, exp_inf, d_clr,
-                           beta1, beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream);
+    return cs_train<false, HGNN_OPT_ADAMAX>(cfg, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, grads, exp_avg,
+                                            exp_inf, d_clr, 1, beta1, beta2, eps, weight_decay, d_stats, d_out, d_err,
+                                            tag, stream);
 }
 
 int hgnn_ccn_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
@@ -1088,8 +1094,28 @@ int hgnn_ccn_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, cons
                               float* const* exp_avg, float* const* exp_inf, const float* d_clr, double beta1,
                               double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
                               int32_t* d_err, int32_t tag, void* stream) {
-    return cs_train<true>(cfg, d_X, d_adj, d_n_batch, d_y, 0.0, 1.0, params, grads, exp_avg, exp_inf, d_clr, beta1,
-                          beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream);
+    return cs_train<true, HGNN_OPT_ADAMAX>(cfg, d_X, d_adj, d_n_batch, d_y, 0.0, 1.0, params, grads, exp_avg, exp_inf,
+                                           d_clr, 1, beta1, beta2, eps, weight_decay, d_stats, d_out, d_err, tag,
+                                           stream);
+}
+
+int hgnn_ccn_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,
+                             const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                             float* const* params, float* const* grads, float* const* state1, float* const* state2,
+                             const float* d_steps, double beta1_or_momentum, double beta2, double eps,
+                             double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag,
+                             void* stream) {
+    if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
+#define CS_TRAIN_OPT(X, O)                                                                                          \
+    cs_train<X, O>(cfg, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, state2, \
+                   d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream)
+    switch (kind) {
+        case HGNN_OPT_ADAMAX: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_ADAMAX) : CS_TRAIN_OPT(false, HGNN_OPT_ADAMAX);
+        case HGNN_OPT_SGD: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_SGD) : CS_TRAIN_OPT(false, HGNN_OPT_SGD);
+        case HGNN_OPT_ADAM: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_ADAM) : CS_TRAIN_OPT(false, HGNN_OPT_ADAM);
+        default: return HGNN_ERR_ARG;
+    }
+#undef CS_TRAIN_OPT
 }
 
 }  // extern "C"

@@ -505,7 +505,7 @@ int launch_dw_readout(const DwDenseArgs& a, hipStream_t s);
 // ---------------------------------------------------------------- optimizer
 // One element of torch.optim.Adamax in torch's operation order (train.hip): g += wd p; m = lerp(m, g, w) with
 // w = 1 - beta1 < 0.5; u = max(beta2 u, |g| + eps); p -= lr_c m / u with lr_c = lr / (1 - beta1^t).  The one
-// definition of the update: k_adamax and the CCN training kernels (ccn_small.hip, ccn2_small_train.hip) all inline it.
+// definition of the update: k_optim (train.hip) and the CCN training kernels (ccn_small.hip, ccn2_small_train.hip) all inline it.
 __device__ __forceinline__ void adamax_elem(float& p, float g, float& m, float& u, float lr_c, float w, float beta2,
                                             float eps, float wd) {
     if (wd != 0.f) g = g + wd * p;
@@ -513,6 +513,87 @@ __device__ __forceinline__ void adamax_elem(float& p, float g, float& m, float& 
     m = m0 + w * (g - m0);  // torch lerp, weight < 0.5
     u = fmaxf(u * beta2, fabsf(g) + eps);
     p = p + (-lr_c) * (m / u);  // addcdiv_(m, u, value = -clr)
+}
+
+// One element of torch.optim.SGD(lr, momentum, weight_decay) (dampening 0, no Nesterov): g += wd p;
+// buf = mu buf + g; p -= lr buf.  A zero buffer gives buf = g, torch's first-step rule, so there is no first-step
+// flag.  Which multiply-adds are fused is fixed here and not left to the compiler (contraction is off in the body):
+// the two `add(x, alpha = s)` forms (g + wd p, p + (-lr) buf) are one fma each, as an elementwise a + s b kernel
+// contracts; buf.mul_(mu).add_(g) is two roundings, as torch's two kernels are.
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float lr, float mu, float wd) {
+#pragma clang fp contract(off)
+    if (wd != 0.f) g = fmaf(wd, p, g);
+    const float t = mu * buf;
+    buf = t + g;
+    p = fmaf(-lr, buf, p);
+}
+
+// One element of torch.optim.Adam(lr, (beta1, beta2), eps, weight_decay) (no amsgrad): g += wd p;
+// m = lerp(m, g, w), w = 1 - beta1 < 0.5; v = beta2 v + (1 - beta2) g g; denom = sqrt(v) / bc2s + eps;
+// p -= lr_c m / denom, with the per-step scalars lr_c = lr / (1 - beta1^t) and bc2s = sqrt(1 - beta2^t).
+// Fused, one fma each: g + wd p, the lerp m + w (g - m), the addcmul a + s (g g) (g g and beta2 v rounded first:
+// torch's pointwise form s * (b * c), and mul_ is its own kernel) and the addcdiv p + (-lr_c)(m / denom).  Not
+// fused: the division, the square root and `+ eps` (add_ after the division's rounding).  Contraction is off in the
+// body, so every kernel that inlines this gets these instructions.
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float lr_c, float bc2s, float w,
+                                          float beta2, float omb2, float eps, float wd) {
+#pragma clang fp contract(off)
+    if (wd != 0.f) g = fmaf(wd, p, g);
+    const float d = g - m;
+    m = fmaf(w, d, m);
+    const float vb = v * beta2;
+    const float gg = g * g;
+    v = fmaf(omb2, gg, vb);
+    const float q = sqrtf(v) / bc2s;
+    const float denom = q + eps;
+    const float r = m / denom;
+    p = fmaf(-lr_c, r, p);
+}
+
+// The optimizer of a training step: which element update a kernel's optimizer stage inlines (HGNN_OPT_* of the
+// header).  OptScalars are the hyper-parameters that stay fixed over a dispatch, combined in double on the host and
+// passed as fp32; the two per-step scalars (c0, c1) travel separately:
+//   ADAMAX  c0 = lr / (1 - beta1^t);                          a = 1 - beta1
+//   SGD     c0 = lr;                                          a = momentum
+//   ADAM    c0 = lr / (1 - beta1^t), c1 = sqrt(1 - beta2^t);  a = 1 - beta1, omb2 = 1 - beta2
+struct OptScalars {
+    float a, beta2, eps, wd, omb2;
+};
+
+inline OptScalars opt_scalars(int kind, double beta1_or_momentum, double beta2, double eps, double wd) {
+    OptScalars h;
+    h.a = kind == HGNN_OPT_SGD ? (float)beta1_or_momentum : (float)(1.0 - beta1_or_momentum);
+    h.beta2 = (float)beta2;
+    h.omb2 = (float)(1.0 - beta2);
+    h.eps = (float)eps;
+    h.wd = (float)wd;
+    return h;
+}
+
+// Element q of one tensor: load, update, store -- s1 / s2 are exp_avg / exp_inf (Adamax), momentum_buffer / unused
+// (SGD, s2 is never touched) or exp_avg / exp_avg_sq (Adam).  p, s1 and s2 are plain pointers: the training kernels
+// read parameters they wrote earlier in the dispatch.
+template <int OPT>
+__device__ __forceinline__ void optim_at(float* pp, float g, float* s1, float* s2, int q, float c0, float c1,
+                                         const OptScalars& h) {
+    if constexpr (OPT == HGNN_OPT_SGD) {
+        float p = pp[q], b = s1[q];
+        sgd_elem(p, g, b, c0, h.a, h.wd);
+        s1[q] = b;
+        pp[q] = p;
+    } else if constexpr (OPT == HGNN_OPT_ADAM) {
+        float p = pp[q], m = s1[q], v = s2[q];
+        adam_elem(p, g, m, v, c0, c1, h.a, h.beta2, h.omb2, h.eps, h.wd);
+        s1[q] = m;
+        s2[q] = v;
+        pp[q] = p;
+    } else {
+        float p = pp[q], m = s1[q], u = s2[q];
+        adamax_elem(p, g, m, u, c0, h.a, h.beta2, h.eps, h.wd);
+        s1[q] = m;
+        s2[q] = u;
+        pp[q] = p;
+    }
 }
 
 // ---------------------------------------------------------------- cross-entropy

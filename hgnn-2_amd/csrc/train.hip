@@ -7,8 +7,9 @@
 //    of utils.evaluation (functions/utils.py:98-102) and the RunningAverage
 //    updates of both (functions/utils.py:134-146) -- one block, no host sync
 //    (the reference calls .item() twice per batch).
-//  * hgnn_adamax_step: torch.optim.Adamax (scripts/main_gnn_qm9.py:185) over every
-//    parameter tensor in one launch (multi-tensor apply): per element
+//  * hgnn_optim_step: torch.optim.Adamax (scripts/main_gnn_qm9.py:185), torch.optim.SGD or
+//    torch.optim.Adam (scripts/main_gnn.py:161-167) over every parameter tensor in one
+//    launch (multi-tensor apply); the element updates are in kernels.h.  Adamax, per element
 //      g += wd p;  m = lerp(m, g, 1 - b1);  u = max(b2 u, |g| + eps);
 //      p -= lr / (1 - b1^t) * m / u
 //    in torch's operation order (lerp as a + w (b - a) for w < 0.5).
@@ -89,30 +90,28 @@ __global__ void __launch_bounds__(256) k_xent_loss(const float* __restrict__ out
     }
 }
 
-constexpr int ADAMAX_MAX = 64;
+constexpr int OPT_MAX = 64;
 
-struct AdamaxTable {
-    float* p[ADAMAX_MAX];
-    const float* g[ADAMAX_MAX];
-    float* m[ADAMAX_MAX];
-    float* u[ADAMAX_MAX];
-    int n[ADAMAX_MAX];
-    int start[ADAMAX_MAX + 1];  // prefix of per-tensor block counts
+struct OptTable {
+    float* p[OPT_MAX];
+    const float* g[OPT_MAX];
+    float* s1[OPT_MAX];
+    float* s2[OPT_MAX];  // SGD: not read
+    int n[OPT_MAX];
+    int start[OPT_MAX + 1];  // prefix of per-tensor block counts
     int count;
 };
 
-__global__ void __launch_bounds__(256) k_adamax(AdamaxTable tab, float lr_c, float w, float beta2, float eps,
-                                                float wd) {
+// One optimizer step over up to 64 tensors; OPT picks the element update (kernels.h optim_at), c0 / c1 are the
+// step's scalars.
+template <int OPT>
+__global__ void __launch_bounds__(256) k_optim(OptTable tab, float c0, float c1, OptScalars h) {
     // block -> tensor by the block prefix (uniform scan over <= 64 entries)
     int t = 0;
     while (t + 1 < tab.count && (int)blockIdx.x >= tab.start[t + 1]) ++t;
     const int i = ((int)blockIdx.x - tab.start[t]) * 256 + threadIdx.x;
     if (i >= tab.n[t]) return;
-    float p = tab.p[t][i], m = tab.m[t][i], u = tab.u[t][i];
-    adamax_elem(p, tab.g[t][i], m, u, lr_c, w, beta2, eps, wd);
-    tab.m[t][i] = m;
-    tab.u[t][i] = u;
-    tab.p[t][i] = p;
+    optim_at<OPT>(tab.p[t], tab.g[t][i], tab.s1[t], tab.s2[t], i, c0, c1, h);
 }
 
 // Evaluation meters of scripts/test_ccn.py:34-67 over G graphs' outputs: [mean_g MSE_g, mean_g MAE_g] with the
@@ -232,39 +231,53 @@ int hgnn_ccn_eval_xent(const float* d_out, const float* d_y, int n_graphs, int n
     return HGNN_OK;
 }
 
-int hgnn_adamax_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                     float* const* exp_inf, const int64_t* numel, double lr, double beta1, double beta2,
-                     double eps, double weight_decay, long long step, void* stream) {
-    if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_inf || !numel)) || step < 1)
+int hgnn_optim_step(int kind, int n_tensors, float* const* params, const float* const* grads, float* const* state1,
+                    float* const* state2, const int64_t* numel, double lr, double beta1_or_momentum, double beta2,
+                    double eps, double weight_decay, long long step, void* stream) {
+    if (kind != HGNN_OPT_ADAMAX && kind != HGNN_OPT_SGD && kind != HGNN_OPT_ADAM) return HGNN_ERR_ARG;
+    const bool two = kind != HGNN_OPT_SGD;  // whether state2 is used
+    if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !state1 || (two && !state2) || !numel)) || step < 1)
         return HGNN_ERR_ARG;
-    // hyper-parameters combine in double (Python floats) and reach the kernel as fp32
-    // scalars, as torch's scalar arguments do: clr = lr / (1 - beta1^step), w = 1 - beta1
-    const double bc = 1.0 - pow(beta1, (double)step);
-    const float lr_c = (float)(lr / bc);
-    const float w = (float)(1.0 - beta1);
+    for (int k = 0; k < n_tensors; ++k) {
+        if (numel[k] < 0 || numel[k] > (1ll << 30)) return HGNN_ERR_ARG;
+        if (numel[k] > 0 && (!params[k] || !grads[k] || !state1[k] || (two && !state2[k]))) return HGNN_ERR_ARG;
+    }
+    // hyper-parameters combine in double (Python floats) and reach the kernel as fp32 scalars, as torch's scalar
+    // arguments do: Adamax / Adam c0 = lr / (1 - beta1^step), Adam c1 = sqrt(1 - beta2^step); SGD c0 = lr
+    float c0 = (float)lr, c1 = 0.f;
+    if (kind != HGNN_OPT_SGD) c0 = (float)(lr / (1.0 - pow(beta1_or_momentum, (double)step)));
+    if (kind == HGNN_OPT_ADAM) c1 = (float)sqrt(1.0 - pow(beta2, (double)step));
+    const OptScalars h = opt_scalars(kind, beta1_or_momentum, beta2, eps, weight_decay);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int base = 0; base < n_tensors; base += ADAMAX_MAX) {
-        AdamaxTable tab{};
+    for (int base = 0; base < n_tensors; base += OPT_MAX) {
+        OptTable tab{};
         tab.count = 0;
         int blocks = 0;
-        for (int k = base; k < n_tensors && tab.count < ADAMAX_MAX; ++k) {
-            if (numel[k] < 0 || numel[k] > (1ll << 30)) return HGNN_ERR_ARG;
+        for (int k = base; k < n_tensors && tab.count < OPT_MAX; ++k) {
             const int c = tab.count++;
             tab.p[c] = params[k];
             tab.g[c] = grads[k];
-            tab.m[c] = exp_avg[k];
-            tab.u[c] = exp_inf[k];
+            tab.s1[c] = state1[k];
+            tab.s2[c] = two ? state2[k] : nullptr;
             tab.n[c] = (int)numel[k];
             tab.start[c] = blocks;
             blocks += (int)ceil_div<long long>(numel[k], 256);
         }
         tab.start[tab.count] = blocks;
         if (blocks == 0) continue;
-        HGNN_KLAUNCH(k_adamax, dim3(blocks), dim3(256), 0, s, tab, lr_c, w, (float)beta2, (float)eps,
-                           (float)weight_decay);
+        if (kind == HGNN_OPT_SGD) HGNN_KLAUNCH(k_optim<HGNN_OPT_SGD>, dim3(blocks), dim3(256), 0, s, tab, c0, c1, h);
+        else if (kind == HGNN_OPT_ADAM) HGNN_KLAUNCH(k_optim<HGNN_OPT_ADAM>, dim3(blocks), dim3(256), 0, s, tab, c0, c1, h);
+        else HGNN_KLAUNCH(k_optim<HGNN_OPT_ADAMAX>, dim3(blocks), dim3(256), 0, s, tab, c0, c1, h);
         HGNN_LAUNCH_CHECK();
     }
     return HGNN_OK;
+}
+
+int hgnn_adamax_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                     float* const* exp_inf, const int64_t* numel, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, long long step, void* stream) {
+    return hgnn_optim_step(HGNN_OPT_ADAMAX, n_tensors, params, grads, exp_avg, exp_inf, numel, lr, beta1, beta2, eps,
+                           weight_decay, step, stream);
 }
 
 }  // extern "C"

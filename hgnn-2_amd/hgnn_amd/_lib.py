@@ -18,6 +18,8 @@ LIB_PATH = os.environ.get("HGNN_LIB_PATH") or os.path.join(os.path.dirname(os.pa
                                                             "libhgnn_amd.so")
 
 HGNN_OK = 0
+# hgnn_optimizer (include/hgnn_amd.h)
+OPT_KIND = {"adamax": 0, "sgd": 1, "adam": 2}
 STATUS = {0: "ok", 1: "invalid argument", 2: "unsupported configuration", 3: "HIP runtime error",
           4: "index out of range"}
 DEVERR = {
@@ -178,6 +180,14 @@ SIGNATURES = {
     "hgnn_xent_loss": ([_VP, _VP, _I, _I, _VP, _VP, _VP, _VP], _I),
     "hgnn_adamax_step": ([_I, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _VP], _I),
+    "hgnn_optim_step": ([_I, _I, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                         ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _VP], _I),
+    "hgnn_ccn_small_train_opt": ([ctypes.POINTER(CcnConfig), _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,
+                                  ctypes.c_double, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double,
+                                  ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _I, _VP], _I),
+    "hgnn_ccn2_small_train_opt": ([ctypes.POINTER(CcnConfig), _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,
+                                   ctypes.c_double, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _VP, _I, _VP], _I),
     "hgnn_conv1x1_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
     "hgnn_conv1x1_forward": ([_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP], _I),
     "hgnn_conv1x1_backward": ([_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _VP], _I),

@@ -12,7 +12,8 @@ device and no host synchronisation:
                both RunningAverages, in one kernel
   backward     the executor's backward (autograd seeded with dloss)
   all-reduce   optional gradient bucket all-reduce (hgnn_amd.dp.GradAllReduce)
-  optimizer    hgnn_adamax_step: Adamax over every parameter in one launch
+  optimizer    hgnn_optim_step: Adamax (the default; SGD with momentum or Adam, the drivers'
+               --optim) over every parameter in one launch
 
 Classification (the reference's `mean == 0` branch, scripts/train_mnb.py:50-51: T cast to
 class indices, the drivers' nn.CrossEntropyLoss, scripts/main_generate.py:147) uses
@@ -20,6 +21,7 @@ hgnn_xent_loss instead; the MAE meters stay untouched as in the reference.
 """
 
 import ctypes
+import math
 import os
 
 import torch
@@ -74,16 +76,80 @@ class _TargetWord:
             raise RuntimeError(self.MESSAGE)
 
 
-class TrainStep:
+class _Optimizer:
+    """The optimizer of a training step, shared by TrainStep and CcnTrainStep: the drivers' --optim
+    sgd|adamax|adam and --momentum (scripts/main_ccn.py:59-62, 155-162, scripts/main_gnn.py:161-167), i.e.
+    torch.optim.Adamax(params, lr), torch.optim.SGD(params, lr, momentum=momentum) or torch.optim.Adam(params, lr),
+    with betas, eps and weight_decay where the optimizer has them.  State: adamax exp_avg and exp_inf, adam exp_avg
+    and exp_avg_sq, sgd momentum_buffer.  .lr is read at every step, so the drivers' damping between epochs
+    (main_ccn.py:183-186) is `step.lr *= damping`."""
+
+    @staticmethod
+    def _check_optimizer(optimizer):
+        if optimizer not in L.OPT_KIND:
+            raise RuntimeError(f"hgnn_amd: optimizer={optimizer!r}: expected \"adamax\", \"sgd\" or \"adam\"")
+
+    def _init_optimizer(self, optimizer, momentum):
+        self._check_optimizer(optimizer)
+        self.optimizer = optimizer
+        self.momentum = float(momentum)
+        self._kind = L.OPT_KIND[optimizer]
+        self.reset_optimizer()
+
+    def reset_optimizer(self):
+        """The drivers build a new optimizer every epoch (scripts/main_gnn_qm9.py:185, scripts/main_ccn.py:155-162):
+        zero state, step 0."""
+        zeros = lambda: [torch.zeros_like(p) for p in self.params]  # noqa: E731
+        if self.optimizer == "sgd":
+            self.momentum_buffer = zeros()
+        elif self.optimizer == "adam":
+            self.exp_avg, self.exp_avg_sq = zeros(), zeros()
+        else:
+            self.exp_avg, self.exp_inf = zeros(), zeros()
+        self.step_count = 0
+
+    def _states(self):
+        """hgnn_optim_step's (state1, state2) as pointer arrays; sgd has no second state."""
+        if self.optimizer == "sgd":
+            return L.ptr_array(self.momentum_buffer), None
+        return L.ptr_array(self.exp_avg), L.ptr_array(self.exp_avg_sq if self.optimizer == "adam" else self.exp_inf)
+
+    def _b1(self):
+        """hgnn_optim_step's beta1_or_momentum."""
+        return self.momentum if self.optimizer == "sgd" else self.betas[0]
+
+    def _optim_step(self, lib, grads, stream):
+        """One step on `grads` (hgnn_optim_step); counts it."""
+        self.step_count += 1
+        s1, s2 = self._states()
+        L.check(lib.hgnn_optim_step(self._kind, len(self.params), L.ptr_array(self.params), L.ptr_array(grads),
+                                    s1, s2, self._numel, self.lr,
+                                    self._b1(), self.betas[1], self.eps, self.weight_decay, self.step_count, stream),
+                f"{self.optimizer} step")
+
+    def _step_scalars(self, t0, n):
+        """The (n, 2) per-step scalars of steps t0 + 1 .. t0 + n for the fused kernels' _opt entries, formed in
+        double as hgnn_optim_step forms its own."""
+        b1, b2 = self.betas
+        if self.optimizer == "sgd":
+            return [(self.lr, 0.0)] * n
+        if self.optimizer == "adam":
+            return [(self.lr / (1.0 - b1 ** t), math.sqrt(1.0 - b2 ** t)) for t in range(t0 + 1, t0 + 1 + n)]
+        return [(self.lr / (1.0 - b1 ** t), 0.0) for t in range(t0 + 1, t0 + 1 + n)]
+
+
+class TrainStep(_Optimizer):
     """One train_with_mnb minibatch step for a GNN_lg / GNN_simple drop-in model.
 
     step(batch) with batch = the 11-tuple of prepare_batch (on the model's device)
     or a hgnn_amd.csr.CsrBatch with targets.  Returns the device tensor `stats`:
     [loss, mae, running loss, running mae] (read it when you log, not per step).
+    optimizer="adamax" (default) | "sgd" | "adam" and momentum: see _Optimizer.
     """
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
-                 grad_allreduce=None, classification=None):
+                 grad_allreduce=None, classification=None, optimizer="adamax", momentum=0.9):
+        self._check_optimizer(optimizer)
         self.model = model
         # the reference's rule (train_mnb.py:50-51): mean == 0 marks generated (classification) data --
         # inferred only from an explicitly passed t_mean; TrainStep(model) is the regression step
@@ -110,13 +176,7 @@ class TrainStep:
         # (HGNN_STRICT=1: checked at once)
         self._targets = _TargetWord(dev)
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
-        self.reset_optimizer()
-
-    def reset_optimizer(self):
-        """The reference builds a new Adamax every epoch (scripts/main_gnn_qm9.py:185): zero state, step 0."""
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_inf = [torch.zeros_like(p) for p in self.params]
-        self.step_count = 0
+        self._init_optimizer(optimizer, momentum)
 
     def reset_running(self):
         """New RunningAverage meters (one pair per train_with_mnb call, scripts/train_mnb.py:34-35)."""
@@ -166,11 +226,7 @@ class TrainStep:
         grads = [p.grad for p in self.params]
         if any(g is None for g in grads):
             raise RuntimeError("hgnn_amd: a parameter received no gradient")
-        self.step_count += 1
-        L.check(lib.hgnn_adamax_step(len(self.params), L.ptr_array(self.params), L.ptr_array(grads),
-                                     L.ptr_array(self.exp_avg), L.ptr_array(self.exp_inf), self._numel, self.lr,
-                                     self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
-                                     stream), "adamax step")
+        self._optim_step(lib, grads, stream)
         return self.stats
 
     def check_targets(self):
@@ -185,9 +241,14 @@ CCN_TRAIN_MAX_GRAPHS = 4096
 # tools/ab_ccn_train.py --order 2 ("The CCN-2D loop without the host"): the kernel's median per graph
 # against the unfused loop's.
 CCN2_TRAIN_FUSED_DEFAULT = True
+# The same decision per optimizer for the kernels' sgd / adam instantiations (hgnn_ccn_small_train_opt,
+# hgnn_ccn2_small_train_opt): (order, optimizer) -> whether fused=None takes the fused kernel.  From
+# profiles/ccn_train_optim_ab.json (tools/ab_ccn_train.py --optim ...): fused where the fused median is at or below
+# the unfused median.
+CCN_TRAIN_FUSED_OPTIM = {(1, "sgd"): True, (1, "adam"): True, (2, "sgd"): True, (2, "adam"): True}
 
 
-class CcnTrainStep:
+class CcnTrainStep(_Optimizer):
     """The per-graph training loop of scripts/train_ccn.py:31-73 for a CCN_1D / CCN_2D drop-in model, and
     the evaluation loop of scripts/test_ccn.py:23-67, without host round trips.
 
@@ -200,7 +261,7 @@ class CcnTrainStep:
       fused2d  hgnn_ccn2_small_train: the same for CCN_2D (graphs of <= 32 nodes, input_feats <= 8,
                hidden_size <= 2, n_outputs <= 256); its one-graph workspace is allocated once per nmax and kept
       unfused  per graph forward_batch on the one-graph slice, hgnn_mse_loss, autograd backward and
-               hgnn_adamax_step: the same arithmetic from the separate entry points (larger graphs, wider
+               hgnn_optim_step: the same arithmetic from the separate entry points (larger graphs, wider
                channels)
 
     fused=None takes a fused kernel wherever hgnn_ccn_small_train_supported or hgnn_ccn2_small_train_supported
@@ -225,11 +286,17 @@ class CcnTrainStep:
 
     fused=None and classification: the kernel's backward LDS layout bounds the graph size by the depth (at the
     generated driver's CCN_1D(5, 2, 2, 10): 31 nodes), so a chunk padded to a larger graph runs unfused.
+
+    optimizer="adamax" (default) | "sgd" | "adam" and momentum (see _Optimizer; scripts/main_ccn.py:155-162): the
+    fused paths are then hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt, the same kernels with their optimizer
+    stage instantiated for it, and the unfused path calls hgnn_optim_step.  Routing is the same; fused=None takes
+    a fused kernel for sgd / adam by CCN_TRAIN_FUSED_OPTIM, the measured default.
     """
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
-                 fused=None, classification=None):
+                 fused=None, classification=None, optimizer="adamax", momentum=0.9):
         from models.compnets.model_ccn import _CCN
+        self._check_optimizer(optimizer)
         if not isinstance(model, _CCN):
             raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
         # the reference's rule (train_ccn.py:39): mean == 0 marks generated (classification) data
@@ -278,13 +345,7 @@ class CcnTrainStep:
         self._mean = torch.tensor(self.t_mean, dtype=torch.float32, device=dev)
         self._div = torch.tensor(self.t_std + 1e-8, dtype=torch.float32, device=dev)
         self._targets = _TargetWord(dev)  # the unfused classification path's and evaluate's error word
-        self.reset_optimizer()
-
-    def reset_optimizer(self):
-        """The driver builds a new Adamax every epoch (scripts/main_ccn_qm9.py:178): zero state, step 0."""
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_inf = [torch.zeros_like(p) for p in self.params]
-        self.step_count = 0
+        self._init_optimizer(optimizer, momentum)
 
     def reset_running(self):
         """New RunningAverage meters (one pair per train_ccn call, scripts/train_ccn.py:28-29)."""
@@ -302,9 +363,11 @@ class CcnTrainStep:
         """The path of a chunk padded to nmax nodes."""
         fused = self.fused
         if fused is None:
-            if self._supported(nmax):
+            one = CCN_TRAIN_FUSED_OPTIM.get((1, self.optimizer), True)
+            two = CCN_TRAIN_FUSED_OPTIM.get((2, self.optimizer), CCN2_TRAIN_FUSED_DEFAULT)
+            if one and self._supported(nmax):
                 return "fused"
-            return "fused2d" if CCN2_TRAIN_FUSED_DEFAULT and self._supported2d(nmax) else "unfused"
+            return "fused2d" if two and self._supported2d(nmax) else "unfused"
         if fused == "ccn2":
             if not self._supported2d(nmax):
                 raise RuntimeError(f"hgnn_amd: fused=\"ccn2\", but nmax = {nmax} is outside the CCN-2D kernel's "
@@ -369,11 +432,26 @@ class CcnTrainStep:
         b1, b2 = self.betas
         # order 2: the kernel's one-graph workspace goes before the error word
         ws = (L.ptr(self._workspace2d(X.shape[1], dev)),) if two else ()
-        name = ("hgnn_ccn2_small_train" if two else "hgnn_ccn_small_train") + ("_xent" if self.classification else "")
+        adamax = self.optimizer == "adamax"
+        name = "hgnn_ccn2_small_train" if two else "hgnn_ccn_small_train"
+        name += ("_xent" if self.classification else "") if adamax else "_opt"
         entry = getattr(lib, name)
         for g0 in range(0, X.shape[0], CCN_TRAIN_MAX_GRAPHS):
             g1 = min(g0 + CCN_TRAIN_MAX_GRAPHS, X.shape[0])
             cfg = self.spec.config(g1 - g0, X.shape[1])
+            if not adamax:
+                # the per-step scalars in double on the host, as hgnn_optim_step forms its own; pinned
+                sc = torch.tensor(self._step_scalars(self.step_count, g1 - g0),
+                                  dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+                err, tag = _word.next(dev)
+                s1, s2 = self._states()
+                L.check(entry(ctypes.byref(cfg), self._kind, int(self.classification), L.ptr(X[g0:g1]),
+                              L.ptr(adj[g0:g1]), L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]),
+                              self.t_mean, self.t_std, L.ptr_array(self.params), L.ptr_array(self._grads), s1, s2,
+                              L.ptr(sc), self._b1(), b2, self.eps, self.weight_decay, L.ptr(self.stats),
+                              L.ptr(self.out[g0:g1]), *ws, err, tag, stream), name)
+                self.step_count += g1 - g0
+                continue
             # the step sizes in double on the host, as hgnn_adamax_step forms its own; pinned, so the copy
             # does not wait for the stream
             clr = torch.tensor([self.lr / (1.0 - b1 ** t) for t in range(self.step_count + 1,
@@ -418,11 +496,7 @@ class CcnTrainStep:
             grads = [p.grad for p in self.params]
             if any(gr is None for gr in grads):
                 raise RuntimeError("hgnn_amd: a parameter received no gradient")
-            self.step_count += 1
-            L.check(lib.hgnn_adamax_step(len(self.params), L.ptr_array(self.params), L.ptr_array(grads),
-                                         L.ptr_array(self.exp_avg), L.ptr_array(self.exp_inf), self._numel, self.lr,
-                                         self.betas[0], self.betas[1], self.eps, self.weight_decay, self.step_count,
-                                         stream), "adamax step")
+            self._optim_step(lib, grads, stream)
             self.out[g].copy_(out.detach()[0])
         if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
             self._targets.watch()

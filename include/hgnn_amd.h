@@ -303,6 +303,30 @@ int hgnn_adamax_step(int n_tensors, float* const* params, const float* const* gr
                      float* const* exp_inf, const int64_t* numel, double lr, double beta1, double beta2,
                      double eps, double weight_decay, long long step, void* stream);
 
+/* The optimizers the reference's drivers build (--optim sgd|adamax|adam, scripts/main_ccn.py:155-162,
+ * scripts/main_gnn.py:161-167): torch.optim.Adamax(params, lr), torch.optim.SGD(params, lr, momentum) and
+ * torch.optim.Adam(params, lr). */
+typedef enum hgnn_optimizer {
+    HGNN_OPT_ADAMAX = 0,
+    HGNN_OPT_SGD = 1,
+    HGNN_OPT_ADAM = 2
+} hgnn_optimizer;
+
+/* hgnn_optim_step: one step of optimizer `kind` on n_tensors parameter tensors, one launch per 64 tensors, in
+ * torch.optim's arithmetic (scalars combined in double, passed to the kernel as fp32):
+ *   HGNN_OPT_ADAMAX  hgnn_adamax_step, bit for bit; state1 = exp_avg, state2 = exp_inf.
+ *   HGNN_OPT_SGD     g += wd p; buf = momentum buf + g; p -= lr buf (dampening 0, no Nesterov; a zero buffer makes
+ *                    the first step buf = g as torch's does).  state1 = momentum_buffer; state2, beta2, eps and
+ *                    step are not used (state2 may be NULL); beta1_or_momentum = momentum.
+ *   HGNN_OPT_ADAM    g += wd p; m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g g;
+ *                    p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps) (no amsgrad).
+ *                    state1 = exp_avg, state2 = exp_avg_sq.
+ * step = the 1-based count of this update (>= 1).  HGNN_ERR_ARG for any other kind. */
+int hgnn_optim_step(int kind, int n_tensors, float* const* params, const float* const* grads,
+                    float* const* state1, float* const* state2, const int64_t* numel, double lr,
+                    double beta1_or_momentum, double beta2, double eps, double weight_decay, long long step,
+                    void* stream);
+
 /* ------------------------------------------------------------------------
  * Covariant compositional networks: CCN_1D / CCN_2D forward + backward.
  *
@@ -451,6 +475,29 @@ int hgnn_ccn2_small_train_xent(const hgnn_ccn_config* cfg, const float* d_X, con
                                const float* d_clr, double beta1, double beta2, double eps, double weight_decay,
                                float* d_stats, float* d_out, void* workspace, int32_t* d_err, int32_t tag,
                                void* stream);
+/* Both loops with the optimizer chosen (scripts/main_ccn.py:59-62, 155-162: --optim sgd|adamax|adam, --momentum):
+ * the same kernels with their optimizer stage instantiated for `kind` (hgnn_optimizer); everything else -- the
+ * validation bits, the error word, the 4096-graph bound, the return codes, supported and the workspace -- is that
+ * of hgnn_ccn_small_train / hgnn_ccn2_small_train.  Per graph the update is hgnn_optim_step's, bit for bit.
+ *   xent: 0 = the MSE loop (t_mean, t_std as above), nonzero = the classification loop (t_mean, t_std ignored).
+ *   state1, state2: as hgnn_optim_step (SGD: state2 and its entries may be NULL and are never touched).
+ *   d_steps (bs, 2): the per-step scalars, formed in double on the host; row k belongs to the k-th APPLIED step of
+ *     the dispatch (a rejected graph consumes no row):
+ *       ADAMAX  [lr / (1 - beta1^t), unused]     SGD  [lr, unused]
+ *       ADAM    [lr / (1 - beta1^t), sqrt(1 - beta2^t)]
+ *   beta1_or_momentum, beta2, eps, weight_decay: as hgnn_optim_step.  HGNN_ERR_ARG for an unknown kind. */
+int hgnn_ccn_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,
+                             const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                             float* const* params, float* const* grads, float* const* state1,
+                             float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
+                             double eps, double weight_decay, float* d_stats, float* d_out, int32_t* d_err,
+                             int32_t tag, void* stream);
+int hgnn_ccn2_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,
+                              const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                              float* const* params, float* const* grads, float* const* state1,
+                              float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
+                              double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
+                              int32_t* d_err, int32_t tag, void* stream);
 /* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
  * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
  * as above.  One block, fp64 sums in a fixed order: the same bits every call. */

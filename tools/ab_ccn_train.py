@@ -15,7 +15,12 @@ profiles/ccn_train_xent_ab.json.
 
 --order 2: the same three paths for CCN_2D(5, 1, 2, 2) on the same 256 QM9-shape graphs, the fused path being
 CcnTrainStep(fused="ccn2"): hgnn_ccn2_small_train; written to profiles/ccn2_train_ab.json.  With --loss xent:
-CCN_2D(5, 2, 2, 2) on those graphs with the label g % 2, written to profiles/ccn2_train_xent_ab.json."""
+CCN_2D(5, 2, 2, 2) on those graphs with the label g % 2, written to profiles/ccn2_train_xent_ab.json.
+
+--optim sgd|adam|adamax (--momentum, default 0.9): the drivers' other optimizers (scripts/main_ccn.py:155-162) on
+all three paths -- torch.optim.SGD(momentum) / Adam / Adamax, hgnn_optim_step, and the fused kernels'
+hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt (adamax: the Adamax entries).  The result is merged into
+profiles/ccn_train_optim_ab.json under the key "order<N>_<loss>_<optim>"; the files above are left alone."""
 import argparse
 import copy
 import json
@@ -38,6 +43,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--loss", choices=("mse", "xent"), default="mse")
     ap.add_argument("--order", type=int, choices=(1, 2), default=1)
+    ap.add_argument("--optim", choices=("sgd", "adam", "adamax"), default=None)
+    ap.add_argument("--momentum", type=float, default=0.9)
     args = ap.parse_args()
     xent, two = args.loss == "xent", args.order == 2
     if xent and two:
@@ -54,7 +61,13 @@ def main():
         nets = {"torch": (CCN_1D(5, 2, 2, 10) if xent else CCN_1D(5, 1, 2, 2)).cuda()}
     nets["unfused"] = copy.deepcopy(nets["torch"])
     nets["fused"] = copy.deepcopy(nets["torch"])
-    opt = torch.optim.Adamax(nets["torch"].parameters(), lr=LR)
+    optim = args.optim or "adamax"
+    if optim == "sgd":
+        opt = torch.optim.SGD(nets["torch"].parameters(), lr=LR, momentum=args.momentum)
+    elif optim == "adam":
+        opt = torch.optim.Adam(nets["torch"].parameters(), lr=LR)
+    else:
+        opt = torch.optim.Adamax(nets["torch"].parameters(), lr=LR)
     crit = torch.nn.CrossEntropyLoss() if xent else torch.nn.MSELoss()
     if xent:
         data = [(x.cuda(), (a + torch.eye(a.shape[0])).cuda(), t[0].view(1).long().cuda()) for x, a, t in graphs]
@@ -72,7 +85,8 @@ def main():
     nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64).cuda()
     Y = torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
     stats = dict(classification=True) if xent else dict(t_mean=MEAN, t_std=STD)
-    steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused") and ("ccn2" if two else True), **stats) for k in ("unfused", "fused")}
+    steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused") and ("ccn2" if two else True), optimizer=optim,
+                             momentum=args.momentum, **stats) for k in ("unfused", "fused")}
 
     def torch_epoch():
         net = nets["torch"]
@@ -102,8 +116,20 @@ def main():
     res["graphs"] = len(graphs)
     res["nmax"] = nmax
     res["epochs"] = len(times["fused"])
+    res["optim"] = optim
     print(json.dumps(res))
     os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
+    if args.optim:
+        path = os.path.join(REPO, "profiles", "ccn_train_optim_ab.json")
+        merged = {}
+        if os.path.exists(path):
+            with open(path) as f:
+                merged = json.load(f)
+        merged[f"order{args.order}_{res['loss']}_{optim}"] = res
+        with open(path, "w") as f:
+            json.dump(merged, f, indent=1, sort_keys=True)
+            f.write("\n")
+        return
     name = ("ccn2_train" if two else "ccn_train") + ("_xent_ab.json" if xent else "_ab.json")
     with open(os.path.join(REPO, "profiles", name), "w") as f:
         json.dump(res, f, indent=1)
