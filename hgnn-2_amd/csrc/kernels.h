@@ -596,6 +596,46 @@ __device__ __forceinline__ void optim_at(float* pp, float g, float* s1, float* s
     }
 }
 
+// ---------------------------------------------------------------- MSE / MAE of a batch
+// One 256-thread block over n elements: T' = normalize_data(T, mean, std) (mean only when std < 1e-5), d = out - T',
+// the fp64 sums of d^2 and |d| in a fixed order (elements strided over the threads, lanes, then the waves in order)
+// and, when dout is given, dout = 2 d / n.  loss = (float)(S / n) and mae = (float)(A / n) are valid on thread 0
+// only.  The one definition of the batch loss: k_mse_loss and k_eval_loss (train.hip) both inline it, so the two
+// write the same bits for the same inputs.
+__device__ __forceinline__ void mse_block(const float* __restrict__ out, const float* __restrict__ t, int n,
+                                          float t_mean, float t_std, float* __restrict__ dout, float& loss,
+                                          float& mae) {
+    __shared__ double red[2][4];
+    double se = 0.0, ae = 0.0;
+    const bool scale = !(t_std < 1e-5f);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        float tn = t[i] - t_mean;
+        if (scale) tn = tn / t_std;
+        const float d = out[i] - tn;
+        se += (double)d * d;
+        ae += fabs((double)d);
+        if (dout) dout[i] = 2.0f * d / (float)n;
+    }
+    se = wave_sum_d(se);
+    ae = wave_sum_d(ae);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][w] = se;
+        red[1][w] = ae;
+    }
+    __syncthreads();
+    loss = mae = 0.f;
+    if (threadIdx.x == 0) {
+        double S = 0.0, A = 0.0;
+        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
+            S += red[0][i];
+            A += red[1][i];
+        }
+        loss = n > 0 ? (float)(S / n) : 0.f;
+        mae = n > 0 ? (float)(A / n) : 0.f;
+    }
+}
+
 // ---------------------------------------------------------------- cross-entropy
 // One row of nn.CrossEntropyLoss on c logits (train.hip): the class index of a target stored as float (a
 // LongTensor cast truncates toward zero); false if it is no integer in [0, c).

@@ -13,6 +13,8 @@
 //      g += wd p;  m = lerp(m, g, 1 - b1);  u = max(b2 u, |g| + eps);
 //      p -= lr / (1 - b1^t) * m / u
 //    in torch's operation order (lerp as a + w (b - a) for w < 0.5).
+//  * hgnn_eval_loss / hgnn_eval_xent: the AverageMeters of scripts/test_mnb.py:25-92 accumulated on the device
+//    over the batches of a set (six doubles), so a validation pass has no host round trip either.
 #include "kernels.h"
 
 namespace hgnn {
@@ -21,33 +23,9 @@ namespace {
 __global__ void __launch_bounds__(256) k_mse_loss(const float* __restrict__ out, const float* __restrict__ t, int n,
                                                   float t_mean, float t_std, float* __restrict__ stats,
                                                   float* __restrict__ dout) {
-    __shared__ double red[2][4];
-    double se = 0.0, ae = 0.0;
-    const bool scale = !(t_std < 1e-5f);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        float tn = t[i] - t_mean;
-        if (scale) tn = tn / t_std;
-        const float d = out[i] - tn;
-        se += (double)d * d;
-        ae += fabs((double)d);
-        if (dout) dout[i] = 2.0f * d / (float)n;
-    }
-    se = wave_sum_d(se);
-    ae = wave_sum_d(ae);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][w] = se;
-        red[1][w] = ae;
-    }
-    __syncthreads();
+    float loss, mae;
+    mse_block(out, t, n, t_mean, t_std, dout, loss, mae);
     if (threadIdx.x == 0) {
-        double S = 0.0, A = 0.0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) {
-            S += red[0][i];
-            A += red[1][i];
-        }
-        const float loss = n > 0 ? (float)(S / n) : 0.f;
-        const float mae = n > 0 ? (float)(A / n) : 0.f;
         stats[0] = loss;
         stats[1] = mae;
         // RunningAverage(momentum = 0.1): first value taken as is, then 0.9 new + 0.1 old
@@ -187,6 +165,69 @@ __global__ void __launch_bounds__(256) k_ccn_eval_xent(const float* __restrict__
     }
 }
 
+// The evaluation meters of scripts/test_mnb.py:25-92 (two AverageMeters, update(value, bs) per batch) kept on the
+// device: m[0] = loss.sum, m[1] = error.sum, m[2] = count, m[3] = hits, m[4] = loss.val, m[5] = error.val.  One
+// thread updates them with plain loads and stores -- stream order serialises the batches of a set -- in double,
+// product and sum rounded separately as AverageMeter's Python floats are.  This is the regression branch
+// (test_mnb.py:52, 64-70): the batch loss and MAE are k_mse_loss's (mse_block), bit for bit.
+__global__ void __launch_bounds__(256) k_eval_loss(const float* __restrict__ out, const float* __restrict__ t, int n,
+                                                   int rows, float t_mean, float t_std, double* __restrict__ m) {
+    float loss, mae;
+    mse_block(out, t, n, t_mean, t_std, nullptr, loss, mae);
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        const double ls = (double)loss * (double)rows;
+        const double es = (double)mae * (double)rows;
+        m[0] = m[0] + ls;
+        m[1] = m[1] + es;
+        m[2] = m[2] + (double)rows;
+        m[4] = (double)loss;
+        m[5] = (double)mae;
+    }
+}
+
+// The classification branch (test_mnb.py:49-50, nn.CrossEntropyLoss): the batch's mean cross entropy as in
+// k_xent_loss (xent_target, xent_row; a thread per row) and the hit count by k_ccn_eval_xent's rule (the first
+// maximum, torch.argmax's tie rule).  A target that is no class index is reported and adds to neither sum; the
+// divisor stays `rows`.  m[1] and m[5] are never written: the reference leaves `error` untouched on this branch.
+__global__ void __launch_bounds__(256) k_eval_xent(const float* __restrict__ out, const float* __restrict__ t,
+                                                   int rows, int c, double* __restrict__ m,
+                                                   uint32_t* __restrict__ err) {
+    __shared__ double red[2][4];
+    double se = 0.0, hit = 0.0;
+    for (int i = threadIdx.x; i < rows; i += 256) {
+        const float* x = out + (long long)i * c;
+        int ti;
+        if (!xent_target(t[i], c, ti)) {
+            atomicOr(err, 1u);
+            continue;
+        }
+        se += (double)xent_row(x, ti, c, 1.0f, nullptr);
+        int am = 0;
+        for (int k = 1; k < c; ++k)
+            if (x[k] > x[am]) am = k;
+        hit += am == ti ? 1.0 : 0.0;
+    }
+    se = wave_sum_d(se);
+    hit = wave_sum_d(hit);
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = se;
+        red[1][threadIdx.x >> 6] = hit;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+        const double S = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        const double H = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        const float loss = (float)(S / rows);
+        const double ls = (double)loss * (double)rows;
+        m[0] = m[0] + ls;
+        m[2] = m[2] + (double)rows;
+        m[3] = m[3] + H;
+        m[4] = (double)loss;
+    }
+}
+
 }  // namespace
 }  // namespace hgnn
 
@@ -227,6 +268,28 @@ int hgnn_ccn_eval_xent(const float* d_out, const float* d_y, int n_graphs, int n
     if (!d_out || !d_y || !d_res || !d_err || n_graphs < 0 || n_out < 1) return HGNN_ERR_ARG;
     HGNN_KLAUNCH(k_ccn_eval_xent, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_y, n_graphs,
                        n_out, d_res, d_err);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+int hgnn_eval_loss(const float* d_out, const float* d_t, int rows, int dim_out, float t_mean, float t_std,
+                   double* d_meters, void* stream) {
+    if (!d_out || !d_t || !d_meters || rows < 0 || dim_out < 1) return HGNN_ERR_ARG;
+    if ((long long)rows * dim_out >= (1ll << 31)) return HGNN_ERR_ARG;
+    if (rows == 0) return HGNN_OK;  // an empty batch updates no meter
+    HGNN_KLAUNCH(k_eval_loss, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_t, rows * dim_out,
+                       rows, t_mean, t_std, d_meters);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+int hgnn_eval_xent(const float* d_out, const float* d_t, int rows, int c, double* d_meters, uint32_t* d_err,
+                   void* stream) {
+    if (!d_out || !d_t || !d_meters || !d_err || rows < 0 || c < 1) return HGNN_ERR_ARG;
+    if ((long long)rows * c >= (1ll << 31)) return HGNN_ERR_ARG;
+    if (rows == 0) return HGNN_OK;
+    HGNN_KLAUNCH(k_eval_xent, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), d_out, d_t, rows, c,
+                       d_meters, d_err);
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
 }

@@ -178,6 +178,8 @@ SIGNATURES = {
                                _VP], _I),
     "hgnn_mse_loss": ([_VP, _VP, _I, ctypes.c_float, ctypes.c_float, _VP, _VP, _VP], _I),
     "hgnn_xent_loss": ([_VP, _VP, _I, _I, _VP, _VP, _VP, _VP], _I),
+    "hgnn_eval_loss": ([_VP, _VP, _I, _I, ctypes.c_float, ctypes.c_float, _VP, _VP], _I),
+    "hgnn_eval_xent": ([_VP, _VP, _I, _I, _VP, _VP, _VP], _I),
     "hgnn_adamax_step": ([_I, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                           ctypes.c_double, ctypes.c_double, ctypes.c_longlong, _VP], _I),
     "hgnn_optim_step": ([_I, _I, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double,

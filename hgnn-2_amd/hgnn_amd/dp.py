@@ -26,6 +26,8 @@ which tests/test_dp_cpu.py and tests/test_gpu_dp.py check.
   statistics.
 * GradAllReduce: the single flat all-reduce for any module (used by TrainStep
   when no executor events are available).
+* sum_meters: the one collective of an evaluation pass -- TrainStep's meters are sums and counts, so their
+  sum over the ranks is the AverageMeter over all ranks' shards (TrainStep.eval_result(group=...)).
 """
 
 import weakref
@@ -120,6 +122,21 @@ def average_running_stats(model, group=None):
         views.append(flat[off:off + t.numel()].view_as(t))
         off += t.numel()
     torch._foreach_copy_(ts, views)
+
+
+def sum_meters(meters, group=None):
+    """The evaluation meters of TrainStep (hgnn_eval_loss / hgnn_eval_xent: loss.sum, error.sum, count, hits,
+    loss.val, error.val) over all ranks' shards: a copy whose slots 0 to 3 -- sums and counts, so that one
+    collective gives the global AverageMeter -- are summed over the group in float64; slots 4 and 5 (the last
+    batch's values) stay the rank's own.  With no initialised process group the copy is returned unchanged.  CPU
+    and device tensors."""
+    out = meters.detach().to(torch.float64).clone()
+    if not dist.is_available() or not dist.is_initialized():
+        return out
+    head = out[:4].clone()
+    dist.all_reduce(head, op=dist.ReduceOp.SUM, group=group)
+    out[:4] = head
+    return out
 
 
 class LayerBucketAllReduce:

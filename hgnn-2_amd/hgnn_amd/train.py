@@ -18,6 +18,11 @@ device and no host synchronisation:
 Classification (the reference's `mean == 0` branch, scripts/train_mnb.py:50-51: T cast to
 class indices, the drivers' nn.CrossEntropyLoss, scripts/main_generate.py:147) uses
 hgnn_xent_loss instead; the MAE meters stay untouched as in the reference.
+
+The other loop of the drivers, test_with_mnb (scripts/test_mnb.py:25-92: per batch a forward in eval mode, the
+criterion's .item() and utils.evaluation(...).item() into two AverageMeters), is TrainStep.evaluate: hgnn_eval_loss /
+hgnn_eval_xent accumulate the meters on the device over the batches of a set, and eval_result reads them once.
+train_epoch and eval_epoch are train_with_mnb and test_with_mnb over a data set.
 """
 
 import ctypes
@@ -27,6 +32,7 @@ import os
 import torch
 
 from . import _lib as L
+from .dp import sum_meters
 
 
 class _TargetWord:
@@ -145,6 +151,9 @@ class TrainStep(_Optimizer):
     or a hgnn_amd.csr.CsrBatch with targets.  Returns the device tensor `stats`:
     [loss, mae, running loss, running mae] (read it when you log, not per step).
     optimizer="adamax" (default) | "sgd" | "adam" and momentum: see _Optimizer.
+
+    Evaluation (test_with_mnb): reset_eval(), evaluate(batch) per batch, eval_result() -- or eval_epoch(data, task,
+    bs) for all three; train_epoch(data, task, bs) is train_with_mnb.
     """
 
     def __init__(self, model, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
@@ -172,6 +181,9 @@ class TrainStep(_Optimizer):
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError("hgnn_amd: TrainStep needs contiguous float32 parameters")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
+        # the evaluation meters (hgnn_eval_loss / hgnn_eval_xent): loss.sum, error.sum, count, hits, loss.val,
+        # error.val
+        self.eval_meters = torch.zeros(6, dtype=torch.float64, device=dev)
         # the class-target error word, checked at the next step without synchronising the stream
         # (HGNN_STRICT=1: checked at once)
         self._targets = _TargetWord(dev)
@@ -181,6 +193,10 @@ class TrainStep(_Optimizer):
     def reset_running(self):
         """New RunningAverage meters (one pair per train_with_mnb call, scripts/train_mnb.py:34-35)."""
         self.stats.zero_()
+
+    def reset_eval(self):
+        """New AverageMeters (one pair per test_with_mnb call, scripts/test_mnb.py:32-33)."""
+        self.eval_meters.zero_()
 
     def _forward(self, batch):
         from .csr import CsrBatch
@@ -196,6 +212,16 @@ class TrainStep(_Optimizer):
             out = m([X, W], Nb, mask)
         return out, T
 
+    def _check_target_shape(self, out, T):
+        if self.classification:
+            if out.shape[1] < 2:
+                raise RuntimeError("hgnn_amd: classification needs dim_output >= 2 (cross-entropy over one "
+                                   "class is identically 0); pass t_mean != 0 or classification=False")
+            if T.numel() != out.shape[0]:
+                raise RuntimeError(f"hgnn_amd: class targets {tuple(T.shape)} do not match {out.shape[0]} rows")
+        elif T.numel() != out.numel():
+            raise RuntimeError(f"hgnn_amd: targets {tuple(T.shape)} do not match the output {tuple(out.shape)}")
+
     def __call__(self, batch):
         lib = L.lib()
         self._targets.poll(block=False)
@@ -206,18 +232,12 @@ class TrainStep(_Optimizer):
         T = T.to(torch.float32).contiguous()
         stream = L.stream_handle(out.device)
         dout = torch.empty_like(out)
+        self._check_target_shape(out, T)
         if self.classification:
-            if out.shape[1] < 2:
-                raise RuntimeError("hgnn_amd: classification needs dim_output >= 2 (cross-entropy over one "
-                                   "class is identically 0); pass t_mean != 0 or classification=False")
-            if T.numel() != out.shape[0]:
-                raise RuntimeError(f"hgnn_amd: class targets {tuple(T.shape)} do not match {out.shape[0]} rows")
             L.check(lib.hgnn_xent_loss(L.ptr(out.detach()), L.ptr(T), out.shape[0], out.shape[1], L.ptr(self.stats),
                                        L.ptr(dout), L.ptr(self._targets.dev), stream), "cross-entropy loss")
             self._targets.watch()
         else:
-            if T.numel() != out.numel():
-                raise RuntimeError(f"hgnn_amd: targets {tuple(T.shape)} do not match the output {tuple(out.shape)}")
             L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(T), out.numel(), self.t_mean, self.t_std,
                                       L.ptr(self.stats), L.ptr(dout), stream), "mse loss")
         torch.autograd.backward(out, dout)
@@ -230,8 +250,97 @@ class TrainStep(_Optimizer):
         return self.stats
 
     def check_targets(self):
-        """Raise if a classification step saw a target outside [0, dim_output) (host sync)."""
+        """Raise if a classification step or evaluation saw a target outside [0, dim_output) (host sync)."""
         self._targets.check()
+
+    def evaluate(self, batch):
+        """One batch of test_with_mnb (scripts/test_mnb.py:42-70): the forward in eval mode under no_grad (the
+        model's mode is restored afterwards), then hgnn_eval_loss -- or hgnn_eval_xent on the classification branch
+        -- adds the batch to the device tensor `eval_meters` = [loss.sum, error.sum, count, hits, loss.val,
+        error.val], which is returned.  batch as for __call__.  No host synchronisation; parameters, gradients, BN
+        running statistics, the optimizer state, step_count and stats are not touched.  reset_eval() starts a set,
+        eval_result() reads it."""
+        lib = L.lib()
+        m = self.model
+        if self.classification:
+            self._targets.poll(block=False)
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                out, T = self._forward(batch)
+        finally:
+            m.train(was_training)
+        out = out.detach().contiguous()
+        T = T.to(torch.float32).contiguous()
+        self._check_target_shape(out, T)
+        stream = L.stream_handle(out.device)
+        if self.classification:
+            L.check(lib.hgnn_eval_xent(L.ptr(out), L.ptr(T), out.shape[0], out.shape[1], L.ptr(self.eval_meters),
+                                       L.ptr(self._targets.dev), stream), "hgnn_eval_xent")
+            self._targets.watch()
+        else:
+            L.check(lib.hgnn_eval_loss(L.ptr(out), L.ptr(T), out.shape[0], out.shape[1], self.t_mean, self.t_std,
+                                       L.ptr(self.eval_meters), stream), "hgnn_eval_loss")
+        return self.eval_meters
+
+    def eval_result(self, accuracy=False, group=None):
+        """(loss.avg, error.avg) of the set evaluated since reset_eval(): the one host read.  The averages are
+        formed in Python doubles, sum / count as AverageMeter does; a zero count gives zeros (AverageMeter's
+        initial state).  Classification: (loss.avg, 0.0) as the reference returns (error is never updated there);
+        accuracy=True adds hits / count as a third value.  group: the sums and counts are first summed over the
+        process group (hgnn_amd.dp.sum_meters), so every rank gets the average over all ranks' shards.  A bad class
+        target shows at check_targets() (or at once under HGNN_STRICT=1), as for a training step."""
+        if accuracy and not self.classification:
+            raise RuntimeError("hgnn_amd: eval_result(accuracy=True) needs a classification step")
+        m = sum_meters(self.eval_meters, group).tolist()
+        count = m[2]
+        loss = m[0] / count if count else 0.0
+        if self.classification:
+            return (loss, 0.0, m[3] / count if count else 0.0) if accuracy else (loss, 0.0)
+        return loss, (m[1] / count if count else 0.0)
+
+    def _batches(self, data, task, bs, dense):
+        """The batches of one epoch in the order of functions.batching.get_batches(n, bs, data, False, False), on
+        the model's device.  data: a list of reference instances [x, A, t, ...] -- CsrBatch(J=model.J,
+        dual=model.dual), so GNN_simple gets its node-graph-only batch; dense=True: full 7-tuples through
+        prepare_batch -- or a hgnn_amd.dataset.GraphPack (pack.batches)."""
+        from functions.batching import get_batches, prepare_batch
+        from .csr import CsrBatch
+        from .dataset import GraphPack
+        m = self.model
+        dev = self.params[0].device
+        pack = isinstance(data, GraphPack)
+        for idx in get_batches(len(data), bs, data, False, False):
+            if pack:
+                # dense: prepare_batch reads all seven members, whatever the model uses of them
+                for b in data.batches(idx, len(idx), task, J=m.J, dual=m.dual or dense, device=dev, dense=dense):
+                    yield [t.to(dev) for t in b] if dense else b
+                continue
+            part = [data[i] for i in idx]
+            if dense:
+                yield [t.to(dev) for t in prepare_batch(part, task, m.J)]
+            else:
+                targets = torch.tensor([float(d[2][task]) for d in part], dtype=torch.float32)
+                yield CsrBatch([(d[0], d[1]) for d in part], J=m.J, dual=m.dual, targets=targets, device=dev)
+
+    def eval_epoch(self, data, task, bs, accuracy=False, dense=False, group=None):
+        """test_with_mnb(model, data, task, criterion, cuda, bs, mean, std, logger) (scripts/test_mnb.py:25-92): new
+        meters, evaluate per batch, then eval_result(accuracy, group) -- one host read for the whole set."""
+        self.reset_eval()
+        for batch in self._batches(data, task, bs, dense):
+            self.evaluate(batch)
+        return self.eval_result(accuracy, group)
+
+    def train_epoch(self, data, task, bs, dense=False):
+        """train_with_mnb (scripts/train_mnb.py:25-94): new RunningAverages, one step per batch in list order (the
+        reference's shuffle is off in its own call too); returns (losses.val, error.val), read once at the end.
+        The optimizer is not reset: the drivers build a new one per epoch themselves (reset_optimizer())."""
+        self.reset_running()
+        for batch in self._batches(data, task, bs, dense):
+            self(batch)
+        s = self.stats.tolist()
+        return s[2], s[3]
 
 
 # graphs per hgnn_ccn_small_train / hgnn_ccn2_small_train dispatch (csrc/ccn_small.hip CS_TRAIN_GMAX,

@@ -303,6 +303,30 @@ int hgnn_adamax_step(int n_tensors, float* const* params, const float* const* gr
                      float* const* exp_inf, const int64_t* numel, double lr, double beta1, double beta2,
                      double eps, double weight_decay, long long step, void* stream);
 
+/* The evaluation meters of test_with_mnb (scripts/test_mnb.py:25-92: two AverageMeters, update(value, bs) per
+ * batch), accumulated on the device over the batches of a set.  d_meters: six doubles owned by the caller, zeroed
+ * by the caller at the start of a set:
+ *   [0] loss.sum = sum_b loss_b * rows_b    [1] error.sum = sum_b mae_b * rows_b    [2] count = sum_b rows_b
+ *   [3] hits (classification)               [4] loss.val (last batch)               [5] error.val (last batch)
+ * so loss.avg = [0] / [2], error.avg = [1] / [2], accuracy = [3] / [2].  One 256-thread block per call; fp64 sums
+ * in a fixed order; the meters are updated by one thread with plain loads and stores (stream order serialises the
+ * batches: no atomics, the same bits for the same sequence of calls).
+ * hgnn_eval_loss (test_mnb.py:52, 64-70, mean != 0): d_out, d_t (rows, dim_out); the target normalised as in
+ *   hgnn_mse_loss; loss = MSELoss and mae = utils.evaluation over the rows * dim_out elements -- the bits
+ *   hgnn_mse_loss writes to d_stats[0..1] for the same inputs -- then, in double, [0] += loss * rows,
+ *   [1] += mae * rows, [2] += rows, [4] = loss, [5] = mae.
+ * hgnn_eval_xent (test_mnb.py:49-50, mean == 0, nn.CrossEntropyLoss): d_out (rows, c) logits, d_t (rows,) class
+ *   indices stored as float; loss = the mean cross entropy as hgnn_xent_loss forms it; [0] += loss * rows,
+ *   [2] += rows, [3] += the rows whose first maximum (torch.argmax's tie rule) is the target, [4] = loss; [1] and
+ *   [5] are never written.  A target that is not an integer in [0, c) ORs 1 into *d_err and adds to neither the
+ *   loss nor the hits; the divisor stays rows.
+ * rows == 0 writes nothing and returns HGNN_OK.  HGNN_ERR_ARG, before any launch: a null pointer, rows < 0,
+ * dim_out < 1, c < 1, rows * dim_out (rows * c) >= 2^31. */
+int hgnn_eval_loss(const float* d_out, const float* d_t, int rows, int dim_out, float t_mean, float t_std,
+                   double* d_meters, void* stream);
+int hgnn_eval_xent(const float* d_out, const float* d_t, int rows, int c, double* d_meters, uint32_t* d_err,
+                   void* stream);
+
 /* The optimizers the reference's drivers build (--optim sgd|adamax|adam, scripts/main_ccn.py:155-162,
  * scripts/main_gnn.py:161-167): torch.optim.Adamax(params, lr), torch.optim.SGD(params, lr, momentum) and
  * torch.optim.Adam(params, lr). */
