@@ -64,6 +64,9 @@ struct ExtractArgs {
     int dbg;           // diagnostics (HGNN_XR_DBG, k_extract_reg): 1 = stop after the loads, 2 = after the marks
 };
 int launch_extract(const ExtractArgs& a, hipStream_t s);
+// the kernel launch_extract takes for these arguments under the process's switches: 0 general (k_extract),
+// 1 LDS-staged (k_extract_lds), 2 register-staged (k_extract_reg)
+int extract_variant(const ExtractArgs& a);
 
 // Pack X (bs, f, nmax) -> [nodes][f];  XL (bs, 1, emax) -> [edges][1].
 int launch_pack_nodes(const float* X, int bs, int f, int nmax, BatchMeta m, float* out, hipStream_t s);

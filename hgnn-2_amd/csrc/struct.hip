@@ -821,11 +821,19 @@ static int extract_one(const ExtractArgs& a, dim3 grid, hipStream_t s) {
     return 0;
 }
 
+int extract_variant(const ExtractArgs& a) {
+    const Switches& sw = switches();
+    // HGNN_EXTRACT_LDS=0: the general kernel
+    if (!sw.extract_lds || a.kind0 != 0) return 0;
+    // HGNN_EXTRACT_REG=0: the LDS-staged kernel for the shapes the register-staged one takes
+    if (sw.extract_reg && extract_reg_fits(a)) return 2;
+    return extract_lds_bytes(a) > 0 ? 1 : 0;
+}
+
 int launch_extract(const ExtractArgs& a, hipStream_t s) {
     const Switches& sw = switches();
-    const bool staged = sw.extract_lds;  // HGNN_EXTRACT_LDS=0: the general kernel
-    // HGNN_EXTRACT_REG=0: the LDS-staged kernel for the shapes the register-staged one takes
-    if (staged && sw.extract_reg && a.kind0 == 0 && extract_reg_fits(a)) {
+    const int variant = extract_variant(a);
+    if (variant == 2) {
         ExtractArgs as = a;
         const int dbg = sw.xr_dbg;
         // (diagnostics, HGNN_XR_DBG: a truncated launch ahead of the real one, which then runs as always)
@@ -841,8 +849,8 @@ int launch_extract(const ExtractArgs& a, hipStream_t s) {
         HGNN_LAUNCH_CHECK();
         return 0;
     }
-    const size_t lds = extract_lds_bytes(a);
-    if (staged && lds > 0 && a.kind0 == 0) {
+    if (variant == 1) {
+        const size_t lds = extract_lds_bytes(a);
         switch (a.jtot) {
             case 3: extract_lds_launch<3>(a, lds, s); break;
             case 4: extract_lds_launch<4>(a, lds, s); break;

@@ -93,6 +93,37 @@ class ProbeDw(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("lddy", "lda", "r_cap", "o", "o_real", "split", "k", "nz")]
 
 
+class ProbeExtract(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("W", "WL", "Pm", "Pd", "mask", "mask_lg", "n_batch", "e_batch", "X",
+                                                "XL", "node_off", "edge_off", "totals", "err")] + \
+               [("rows", ctypes.c_void_p * 6), ("entries", ctypes.c_void_p * 6)] + \
+               [(n, ctypes.c_void_p) for n in ("xo", "xlo")] + \
+               [(n, ctypes.c_int32) for n in ("bs", "nmax", "emax", "jtot", "dual", "validate", "f", "variant")]
+
+
+class ProbeList(ctypes.Structure):
+    _fields_ = [("rows", ctypes.c_void_p), ("entries", ctypes.c_void_p), ("stride", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+class ProbeBn(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mean", "std", "w", "b")]
+
+
+class ProbeAggFwd(ctypes.Structure):
+    _fields_ = [("total_rows", ctypes.c_void_p), ("g", ProbeList), ("xg", ctypes.c_void_p), ("gbn", ProbeBn),
+                ("p", ProbeList), ("xp", ctypes.c_void_p), ("pbn", ProbeBn), ("out", ctypes.c_void_p),
+                ("diag", ctypes.c_void_p), ("err", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("cap_rows", "cg", "jtot", "cp", "ldo", "pad_from", "j0", "reserved")]
+
+
+class ProbeAggBwd(ctypes.Structure):
+    _fields_ = [("total_rows", ctypes.c_void_p), ("g", ProbeList), ("ing", ctypes.c_void_p), ("p", ProbeList),
+                ("inp", ctypes.c_void_p), ("out", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("cap_rows", "ldg", "gofs", "jtot", "ldp", "pofs_m", "pofs_d", "c", "ldo",
+                                              "accumulate")]
+
+
 _lib = None
 
 _VP = ctypes.c_void_p
@@ -199,6 +230,12 @@ SIGNATURES = {
     "hgnn_probe_gemm_da": ([ctypes.POINTER(ProbeDa), _VP, _VP], _I),
     "hgnn_probe_dw_workspace_bytes": ([_I, _I, _I, _I], ctypes.c_size_t),
     "hgnn_probe_gemm_dw": ([ctypes.POINTER(ProbeDw), _VP, _VP], _I),
+    "hgnn_probe_extract": ([ctypes.POINTER(ProbeExtract), _VP], _I),
+    "hgnn_probe_pack_nodes": ([_VP, _I, _I, _I, _VP, _VP, _VP], _I),
+    "hgnn_probe_pack_edges": ([_VP, _I, _I, _VP, _VP, _VP], _I),
+    "hgnn_probe_unpack_nodes": ([_VP, _I, _I, _I, _VP, _VP, _VP], _I),
+    "hgnn_probe_agg_fwd": ([ctypes.POINTER(ProbeAggFwd), _VP], _I),
+    "hgnn_probe_agg_bwd": ([ctypes.POINTER(ProbeAggBwd), ctypes.POINTER(ProbeAggBwd), _I, _VP], _I),
 }
 
 

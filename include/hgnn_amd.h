@@ -683,6 +683,90 @@ typedef struct hgnn_probe_dw {
 } hgnn_probe_dw;
 int hgnn_probe_gemm_dw(const hgnn_probe_dw* p, void* workspace, void* stream);
 
+/* ---- The sparse side (csrc/struct.hip, csrc/agg.hip): the batch plan and the structure extraction, the pack /
+ * unpack kernels and the aggregation forward / backward launchers, under the same rules (csrc/probe_sparse.hip).
+ * Row lists are those of csrc/kernels.h StructView: rows [R][2] int32 (start, count), entries of `stride` floats
+ * (column as int bits, then the coefficients). */
+
+/* launch_plan, then launch_extract with entry_stride_w = j_tot <= 3 ? 4 : 8 (the executor's choice).  Every output
+ * is caller-allocated: node_off, edge_off (bs + 1), totals (2), err (1), rows[k] (bs nmax rows for the node kinds 0,
+ * 1, 4; bs emax for the edge kinds 2, 3, 5), entries[k] (bs nmax nmax, bs emax emax entries of the stride for W / WT,
+ * WL / WLT; bs nmax emax entries of 4 floats for PN / PE), xo [nodes][f] and xlo [edges] (optional, with X / XL).
+ * dual = 0: only W, mask, n_batch and kinds 0, 1 are used.  variant (written on the host): the kernel
+ * launch_extract chose -- 0 general, 1 LDS-staged, 2 register-staged. */
+typedef struct hgnn_probe_extract_args {
+    const float* W;
+    const float* WL;
+    const float* Pm;
+    const float* Pd;
+    const float* mask;
+    const float* mask_lg;
+    const int64_t* n_batch;
+    const int64_t* e_batch;
+    const float* X;          /* optional (bs, f, nmax) */
+    const float* XL;         /* optional (bs, 1, emax) */
+    int32_t* node_off;
+    int32_t* edge_off;
+    int32_t* totals;
+    uint32_t* err;
+    void* rows[6];
+    float* entries[6];
+    float* xo;
+    float* xlo;
+    int32_t bs, nmax, emax, jtot, dual, validate, f;
+    int32_t variant;
+} hgnn_probe_extract_args;
+int hgnn_probe_extract(hgnn_probe_extract_args* p, void* stream);
+
+/* launch_pack_nodes / launch_pack_edges / launch_unpack_nodes on the offsets of a plan (bs + 1 each). */
+int hgnn_probe_pack_nodes(const float* d_X, int bs, int f, int nmax, const int32_t* d_node_off, float* d_out,
+                          void* stream);
+int hgnn_probe_pack_edges(const float* d_XL, int bs, int emax, const int32_t* d_edge_off, float* d_out, void* stream);
+int hgnn_probe_unpack_nodes(const float* d_in, int bs, int f, int nmax, const int32_t* d_node_off, float* d_X,
+                            void* stream);
+
+typedef struct hgnn_probe_list {
+    const void* rows;
+    const float* entries;
+    int32_t stride, reserved;
+} hgnn_probe_list;
+
+/* BN applied where the features are read (csrc/kernels.h BnView); mean == NULL: none. */
+typedef struct hgnn_probe_bn {
+    const float* mean;
+    const float* std;
+    const float* w;
+    const float* b;
+} hgnn_probe_bn;
+
+/* csrc/kernels.h AggFwdArgs (launch_agg_fwd); diag [rows][2] and err are optional. */
+typedef struct hgnn_probe_agg_fwd_args {
+    const int32_t* total_rows;
+    hgnn_probe_list g;
+    const float* xg;
+    hgnn_probe_bn gbn;
+    hgnn_probe_list p;
+    const float* xp;
+    hgnn_probe_bn pbn;
+    float* out;
+    float* diag;
+    uint32_t* err;
+    int32_t cap_rows, cg, jtot, cp, ldo, pad_from, j0, reserved;
+} hgnn_probe_agg_fwd_args;
+int hgnn_probe_agg_fwd(const hgnn_probe_agg_fwd_args* p, void* stream);
+
+/* csrc/kernels.h AggBwdArgs.  pair = 0: launch_agg_bwd on a (b unused); pair = 1: launch_agg_bwd_pair(a, b). */
+typedef struct hgnn_probe_agg_bwd_args {
+    const int32_t* total_rows;
+    hgnn_probe_list g;
+    const float* ing;
+    hgnn_probe_list p;
+    const float* inp;
+    float* out;
+    int32_t cap_rows, ldg, gofs, jtot, ldp, pofs_m, pofs_d, c, ldo, accumulate;
+} hgnn_probe_agg_bwd_args;
+int hgnn_probe_agg_bwd(const hgnn_probe_agg_bwd_args* a, const hgnn_probe_agg_bwd_args* b, int pair, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
