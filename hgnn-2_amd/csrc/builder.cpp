@@ -263,6 +263,36 @@ int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
 
+namespace hgnn {
+// The image's field order and byte offsets from the counts (bs, f_in, dual, stride_w, nodes, edges and nnz
+// filled in): the one place they are formed, for the host batcher (csr_batch) and for the device batcher's
+// layout (hgnn_csr_layout_from_counts).
+void csr_layout_offsets(hgnn_csr_layout& L) {
+    const int bs = L.bs, sw = L.stride_w;
+    const int64_t rows_of[K_N] = {L.nodes, L.nodes, L.edges, L.edges, L.nodes, L.edges};
+    const int stride_of[K_N] = {sw, sw, sw, sw, 4, 4};
+    int64_t top = 0;
+    auto take = [&](int64_t bytes) {
+        const int64_t o = top;
+        top += align256(bytes > 0 ? bytes : 1);
+        return o;
+    };
+    L.off_node_off = take(4 * (bs + 1));
+    L.off_edge_off = take(4 * (bs + 1));
+    L.off_totals = take(16);
+    L.off_n_batch = take(8 * bs);
+    L.off_e_batch = take(8 * bs);
+    L.off_x = take(4 * L.nodes * L.f_in);
+    L.off_xl = take(4 * L.edges);
+    for (int k = 0; k < K_N; ++k) {
+        L.rows[k] = (k >= K_WL && !L.dual) ? 0 : rows_of[k];
+        L.off_rows[k] = take(8 * L.rows[k]);
+        L.off_entries[k] = take(4 * stride_of[k] * L.nnz[k]);
+    }
+    L.bytes = top;
+}
+}  // namespace hgnn
+
 extern "C" {
 
 int hgnn_graph_edge_slots(int n, const float* A) {
@@ -330,27 +360,8 @@ static int csr_batch(int bs, const int* n_nodes, const float* const* A, const fl
             for (auto& r : gs[b].pe) L.nnz[K_PE] += (int64_t)r.size();
         }
     }
-    const int64_t rows_of[K_N] = {L.nodes, L.nodes, L.edges, L.edges, L.nodes, L.edges};
     const int stride_of[K_N] = {sw, sw, sw, sw, 4, 4};
-    int64_t top = 0;
-    auto take = [&](int64_t bytes) {
-        const int64_t o = top;
-        top += align256(bytes > 0 ? bytes : 1);
-        return o;
-    };
-    L.off_node_off = take(4 * (bs + 1));
-    L.off_edge_off = take(4 * (bs + 1));
-    L.off_totals = take(16);
-    L.off_n_batch = take(8 * bs);
-    L.off_e_batch = take(8 * bs);
-    L.off_x = take(4 * L.nodes * f_in);
-    L.off_xl = take(4 * L.edges);
-    for (int k = 0; k < K_N; ++k) {
-        L.rows[k] = (k >= K_WL && !dual) ? 0 : rows_of[k];
-        L.off_rows[k] = take(8 * L.rows[k]);
-        L.off_entries[k] = take(4 * stride_of[k] * L.nnz[k]);
-    }
-    L.bytes = top;
+    hgnn::csr_layout_offsets(L);
     *lay = L;
     if (!image) return HGNN_OK;
     if (!expect || memcmp(expect, &L, sizeof(L)) != 0) return HGNN_ERR_ARG;
@@ -434,6 +445,37 @@ int hgnn_csr_batch_build(int bs, const int* n_nodes, const float* const* A, cons
     if (!layout || !image) return HGNN_ERR_ARG;
     hgnn_csr_layout L;
     return csr_batch(bs, n_nodes, A, X, f_in, J, dual, layout, &L, image);
+}
+
+int hgnn_csr_layout_from_counts(int bs, const int32_t* counts, int f_in, int J, int dual, hgnn_csr_layout* layout) {
+    if (bs <= 0 || !counts || !layout || f_in <= 0 || J < 1 || J > 5) return HGNN_ERR_ARG;
+    const int jt = J + 2;
+    hgnn_csr_layout L;
+    memset(&L, 0, sizeof(L));
+    L.bs = bs;
+    L.f_in = f_in;
+    L.j_tot = jt;
+    L.dual = dual ? 1 : 0;
+    L.stride_w = jt <= 3 ? 4 : 8;
+    int flags = 0;
+    for (int b = 0; b < bs; ++b) flags |= counts[(size_t)b * HGNN_PACK_COUNT_WORDS + 8];
+    if (flags & HGNN_PACK_FLAG_INDEX) return HGNN_ERR_INDEX;
+    if (flags & (HGNN_PACK_FLAG_BOUNDS | HGNN_PACK_FLAG_COO)) return HGNN_ERR_UNSUPPORTED;
+    for (int b = 0; b < bs; ++b) {
+        const int32_t* c = counts + (size_t)b * HGNN_PACK_COUNT_WORDS;
+        if (c[0] <= 0 || c[1] < 0) return HGNN_ERR_ARG;
+        L.nmax = std::max(L.nmax, c[0]);
+        L.emax = std::max(L.emax, c[1]);
+        L.nodes += c[0];
+        L.edges += c[1];
+        for (int k = 0; k < K_N; ++k) {
+            if (c[2 + k] < 0) return HGNN_ERR_ARG;
+            L.nnz[k] += c[2 + k];
+        }
+    }
+    hgnn::csr_layout_offsets(L);
+    *layout = L;
+    return HGNN_OK;
 }
 
 }  // extern "C"

@@ -66,6 +66,18 @@ class CsrBatch(ctypes.Structure):
                 ("nodes", ctypes.c_int64), ("edges", ctypes.c_int64)]
 
 
+class PackView(ctypes.Structure):
+    """hgnn_pack_view: a GraphPack's arrays in device memory (the device batcher, csrc/batcher.hip)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("d_node_off", "d_x", "d_adj_off", "d_adj_ij", "d_adj_w",
+                                                "d_targets")] + \
+               [("graphs", ctypes.c_int64), ("f_in", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# hgnn_pack_count's record per graph: {n, m, nnz[6], flags, 0}
+PACK_COUNT_WORDS = 10
+PACK_FLAG_BOUNDS, PACK_FLAG_INDEX, PACK_FLAG_COO = 1, 2, 4
+
+
 class CcnConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("order", "bs", "nmax", "f_in", "hidden", "layers", "n_out", "reserved")]
 
@@ -202,6 +214,11 @@ SIGNATURES = {
     "hgnn_csr_batch_plan": ([_I, _VP, _VP, _I, _I, _I, ctypes.POINTER(CsrLayout)], _I),
     "hgnn_csr_batch_build": ([_I, _VP, _VP, _VP, _I, _I, _I, ctypes.POINTER(CsrLayout), _VP], _I),
     "hgnn_csr_batch_view": ([ctypes.POINTER(CsrLayout), _VP, ctypes.POINTER(CsrBatch)], _I),
+    "hgnn_pack_count": ([ctypes.POINTER(PackView), _I, _I, _VP, _VP], _I),
+    "hgnn_csr_layout_from_counts": ([_I, _VP, _I, _I, _I, ctypes.POINTER(CsrLayout)], _I),
+    "hgnn_csr_batch_build_device_scratch_bytes": ([_I], ctypes.c_size_t),
+    "hgnn_csr_batch_build_device": ([ctypes.POINTER(PackView), _VP, _VP, _I, _I, _I, ctypes.POINTER(CsrLayout), _VP,
+                                     _VP, ctypes.c_size_t, _VP], _I),
     "hgnn_net_backward_ex": ([ctypes.POINTER(NetConfig), ctypes.POINTER(NetInputs), ctypes.POINTER(CsrBatch), _VP, _VP,
                               _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I], _I),
     "hgnn_net_forward_csr": ([ctypes.POINTER(NetConfig), ctypes.POINTER(CsrBatch), _VP, _VP, _VP, _VP, _VP], _I),

@@ -72,6 +72,47 @@ class CsrBatch:
         if targets is not None:
             self.T = torch.as_tensor(targets, dtype=torch.float32).reshape(bs, 1).to(self.image.device)
 
+    @classmethod
+    def from_image(cls, layout, image, targets=None):
+        """A batch over an image that is already resident: `image` (layout.bytes,) uint8 on a device, written by
+        the device batcher (hgnn_csr_batch_build_device; hgnn_amd.dataset.DevicePack) in the layout `layout`
+        (hgnn_csr_layout_from_counts).  Every attribute the constructor sets; `host` is a device-to-host copy
+        made when it is first asked for (lists()).  targets: (bs,) or (bs, 1) tensor on the image's device.
+        No host synchronisation."""
+        if image.dtype != torch.uint8 or image.dim() != 1 or image.numel() != int(layout.bytes) \
+                or not image.is_contiguous():
+            raise RuntimeError("hgnn_amd: CsrBatch.from_image needs a contiguous uint8 image of layout.bytes bytes")
+        self = cls.__new__(cls)
+        lay = layout
+        bs = int(lay.bs)
+        self.layout = lay
+        self.host = None
+        self.image = image
+        self.bs, self.nmax, self.emax = bs, int(lay.nmax), int(lay.emax)
+        self.f_in, self.j_tot, self.dual = int(lay.f_in), int(lay.j_tot), bool(lay.dual)
+        self.nodes, self.edges = int(lay.nodes), int(lay.edges)
+        self.view = L.CsrBatch()
+        L.check(L.lib().hgnn_csr_batch_view(ctypes.byref(lay), ctypes.c_void_p(image.data_ptr()),
+                                            ctypes.byref(self.view)), "csr batch view")
+        self.x = self._f32(lay.off_x, self.nodes * self.f_in).view(self.nodes, self.f_in)
+        self.N_batch = self._i64(lay.off_n_batch, bs)
+        self.E_batch = self._i64(lay.off_e_batch, bs)
+        self.T = None
+        if targets is not None:
+            self.T = targets.to(image.device, torch.float32).reshape(bs, 1)
+        return self
+
+    @property
+    def host(self):
+        """The image in host memory (the constructor builds it there; from_image copies it back on first use)."""
+        if self._host is None:
+            self._host = self.image.cpu()
+        return self._host
+
+    @host.setter
+    def host(self, value):
+        self._host = value
+
     def _f32(self, off, n):
         return self.image[off:off + 4 * n].view(torch.float32)
 

@@ -14,6 +14,8 @@ files through rdkit (preprocessing/preprocessing.py:174-275).  Here:
 * GraphPack.batches -- hgnn_amd.csr.CsrBatch per batch straight from the
   memory-mapped arrays (the executor's layout, csrc/builder.cpp), or the
   reference's dense 11-tuple through functions.batching.prepare_batch.
+* DevicePack (GraphPack.to_device) -- the pack resident on the GPU; the same CsrBatch images built there
+  by the device batcher (csrc/batcher.hip), with no host work per graph.
 * prepare_experiment_sets -- the reference split, same sizes and order.
 * read_xyz / molecule_targets / atom_one_hot -- the QM9 `.xyz` reader: header
   properties, atoms (with the `*^` exponent form), frequencies and SMILES; the
@@ -25,6 +27,7 @@ files through rdkit (preprocessing/preprocessing.py:174-275).  Here:
   is unpinned).
 """
 
+import ctypes
 import json
 import os
 import random
@@ -153,6 +156,106 @@ class GraphPack:
             graphs = [self.graph(i) for i in part]
             targets = torch.tensor([float(t[task]) for _, _, t in graphs], dtype=torch.float32)
             yield CsrBatch([(x, a) for x, a, _ in graphs], J=J, dual=dual, targets=targets, device=device)
+
+    def to_device(self, J=1, dual=True, device="cuda"):
+        """DevicePack(self, J, dual, device): the pack resident on the GPU, batches built there."""
+        return DevicePack(self, J=J, dual=dual, device=device)
+
+
+class DevicePack:
+    """A GraphPack resident on one GPU, with the batcher on the device (csrc/batcher.hip).
+
+    Construction uploads the pack's six arrays once, counts every graph's rows and entries on the device
+    (hgnn_pack_count, once for this J and dual) and reads the records back: the one host synchronisation.
+    batch(idx, task) then sizes the image on the host from the records (hgnn_csr_layout_from_counts) and
+    enqueues hgnn_csr_batch_build_device on the current stream -- the image hgnn_csr_batch_build writes on the
+    host, byte for byte, with no host work per graph and no synchronisation.
+
+    The device builder takes graphs of at most 32 nodes and 72 edge slots and J <= 3; a batch with a larger
+    graph, and every batch at J > 3, is built by the host batcher (pack.batches).  A batch with a graph whose
+    edge-slot construction fails raises IndexError as CsrBatch does, when that batch is asked for.
+    """
+
+    def __init__(self, pack, J=1, dual=True, device="cuda"):
+        from . import _lib as L
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("hgnn_amd: DevicePack lives on a GPU (device=\"cuda\")")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        if len(pack) == 0:
+            raise RuntimeError("hgnn_amd: DevicePack: the pack holds no graphs")
+        self.pack, self.J, self.dual, self.device = pack, int(J), bool(dual), dev
+        self.f_in = int(pack.x.shape[1])
+        host = {k: np.ascontiguousarray(getattr(pack, k)) for k in GraphPack.FILES}
+        for off, total in ((host["node_off"], len(host["x"])), (host["adj_off"], len(host["adj_w"]))):
+            if off[0] != 0 or off[-1] != total or (np.diff(off) < 0).any():
+                raise RuntimeError(f"hgnn_amd: inconsistent graph pack {pack.path}")
+        if host["adj_ij"].shape != (len(host["adj_w"]), 2):
+            raise RuntimeError(f"hgnn_amd: inconsistent graph pack {pack.path}")
+        dtypes = {"node_off": np.int64, "x": np.float32, "adj_off": np.int64, "adj_ij": np.int32,
+                  "adj_w": np.float32, "targets": np.float32}
+        self._arrays = {k: torch.from_numpy(np.array(v, dtype=dtypes[k])).to(dev) for k, v in host.items()}
+        self.targets = self._arrays["targets"]
+        a = self._arrays
+        self._view = L.PackView(*[a[k].data_ptr() for k in GraphPack.FILES], len(pack), self.f_in, 0)
+        self.counts = None  # (graphs, 10) int32 records on the host; None at J > 3 (the host batcher builds all)
+        if self.J <= 3:
+            self._counts = torch.empty(len(pack), L.PACK_COUNT_WORDS, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                L.check(L.lib().hgnn_pack_count(ctypes.byref(self._view), self.J, int(self.dual),
+                                                L.ptr(self._counts), L.stream_handle(dev)), "hgnn_pack_count")
+            self.counts = self._counts.cpu().numpy()
+            bad = np.nonzero(self.counts[:, 8] & L.PACK_FLAG_COO)[0]
+            if len(bad):
+                raise RuntimeError(f"hgnn_amd: graph {int(bad[0])} of {pack.path}: adjacency entries out of range "
+                                   "or not in strictly ascending row-major order")
+
+    def __len__(self):
+        return len(self.pack)
+
+    def batch(self, idx, task):
+        """The CsrBatch of the graphs `idx` (in that order; repeats allowed) with targets[idx, task], built on
+        the device on the current stream."""
+        from . import _lib as L
+        from .csr import CsrBatch
+        idx = [int(i) for i in idx]
+        bs = len(idx)
+        if bs == 0:
+            raise RuntimeError("hgnn_amd: empty batch")
+        if min(idx) < 0 or max(idx) >= len(self.pack):
+            raise IndexError(f"hgnn_amd: graph index outside the pack of {len(self.pack)}")
+        host_path = self.counts is None
+        if not host_path:
+            rec = np.ascontiguousarray(self.counts[np.asarray(idx, dtype=np.int64)])
+            host_path = bool((rec[:, 8] & L.PACK_FLAG_BOUNDS).any())
+        if host_path:
+            return next(self.pack.batches(idx, bs, task, J=self.J, dual=self.dual, device=self.device))
+        lib = L.lib()
+        lay = L.CsrLayout()
+        st = lib.hgnn_csr_layout_from_counts(bs, ctypes.c_void_p(rec.ctypes.data), self.f_in, self.J, int(self.dual),
+                                             ctypes.byref(lay))
+        if st == 4:
+            raise IndexError("hgnn_amd: a graph's edge-slot construction writes past nnz(A) "
+                             "(the reference's graph_operators raises IndexError)")
+        L.check(st, "csr layout from counts")
+        dev = self.device
+        with torch.cuda.device(dev):
+            image = torch.empty(int(lay.bytes), dtype=torch.uint8, device=dev)
+            d_idx = torch.tensor(idx, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            scratch = torch.empty(lib.hgnn_csr_batch_build_device_scratch_bytes(bs), dtype=torch.uint8, device=dev)
+            L.check(lib.hgnn_csr_batch_build_device(ctypes.byref(self._view), L.ptr(self._counts), L.ptr(d_idx), bs,
+                                                    self.J, int(self.dual), ctypes.byref(lay), L.ptr(image),
+                                                    L.ptr(scratch), scratch.numel(), L.stream_handle(dev)),
+                    "csr batch build on the device")
+            targets = self.targets[d_idx.long(), task]
+        return CsrBatch.from_image(lay, image, targets)
+
+    def batches(self, idx, batch_size, task):
+        """One batch per `batch_size` consecutive indices of `idx`, as GraphPack.batches yields them."""
+        idx = list(idx)
+        for b0 in range(0, len(idx), batch_size):
+            yield self.batch(idx[b0:b0 + batch_size], task)
 
 
 # ---------------------------------------------------------------- QM9 .xyz

@@ -304,13 +304,25 @@ class TrainStep(_Optimizer):
         """The batches of one epoch in the order of functions.batching.get_batches(n, bs, data, False, False), on
         the model's device.  data: a list of reference instances [x, A, t, ...] -- CsrBatch(J=model.J,
         dual=model.dual), so GNN_simple gets its node-graph-only batch; dense=True: full 7-tuples through
-        prepare_batch -- or a hgnn_amd.dataset.GraphPack (pack.batches)."""
+        prepare_batch -- or a hgnn_amd.dataset.GraphPack (pack.batches), or a hgnn_amd.dataset.DevicePack built
+        for the model's J and dual (its batches are built on the device; there is no dense form of them)."""
         from functions.batching import get_batches, prepare_batch
         from .csr import CsrBatch
-        from .dataset import GraphPack
+        from .dataset import DevicePack, GraphPack
         m = self.model
         dev = self.params[0].device
         pack = isinstance(data, GraphPack)
+        if isinstance(data, DevicePack):
+            if dense:
+                raise RuntimeError("hgnn_amd: a DevicePack builds CSR batches only (dense=True needs a GraphPack)")
+            if data.J != m.J or data.dual != bool(m.dual):
+                raise RuntimeError(f"hgnn_amd: DevicePack(J={data.J}, dual={data.dual}) does not match the model "
+                                   f"(J={m.J}, dual={bool(m.dual)})")
+            if data.device != dev:
+                raise RuntimeError(f"hgnn_amd: DevicePack on {data.device}, model on {dev}")
+            for idx in get_batches(len(data), bs, data, False, False):
+                yield from data.batches(idx, len(idx), task)
+            return
         for idx in get_batches(len(data), bs, data, False, False):
             if pack:
                 # dense: prepare_batch reads all seven members, whatever the model uses of them

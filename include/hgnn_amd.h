@@ -277,6 +277,56 @@ int hgnn_net_backward_csr(const hgnn_net_config* cfg, const hgnn_csr_batch* batc
                           const float* d_dout, float* const* grads, float* d_dX, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Device batcher (csrc/batcher.hip): the image hgnn_csr_batch_build writes on the host, built on the
+ * device from a resident graph pack -- byte for byte the same image, so everything that runs on a CSR
+ * batch runs on it unchanged.
+ *
+ * The pack is hgnn_amd.dataset.GraphPack's arrays in device memory: node_off (graphs + 1) int64, x
+ * (nodes, f_in) fp32, adj_off (graphs + 1) int64, adj_ij (adj_nnz, 2) int32 local (i, j) in strictly
+ * ascending row-major order per graph, adj_w (adj_nnz) fp32, targets (not read here).
+ *
+ * One workgroup builds one graph in LDS; supported per graph: n <= 32 nodes, m = nnz(A) <= 72 edge
+ * slots (dual), J <= 3.  hgnn_pack_count runs the builder in its counting mode over the whole pack, once
+ * per (pack, J, dual), and writes one record of HGNN_PACK_COUNT_WORDS int32 per graph:
+ *   {n, m (0 without dual), nnz[W, WT, WL, WLT, PN, PE], flags, 0}
+ * A flagged graph's record holds no counts.  The caller reads the records back once, gathers those of a
+ * batch on the host and sizes the image with hgnn_csr_layout_from_counts (no GPU call; the layout
+ * hgnn_csr_batch_plan gives for the same graphs: both form the offsets in one function).
+ * hgnn_csr_batch_build_device then enqueues, with no host synchronisation: the image's memset, the
+ * batch-offset kernel (node_off, edge_off, totals, N_batch, E_batch and each graph's entry starts) and
+ * the per-graph build.  d_counts are the records hgnn_pack_count wrote for this view, J and dual; d_idx
+ * (bs) int32 the batch's graph indices (repeats allowed).  If the records of d_idx do not add up to
+ * `layout`, an index is outside the pack or a record is flagged, nothing but zeros and offsets is
+ * written (the kernels never write past the layout).
+ * ---------------------------------------------------------------------- */
+#define HGNN_PACK_COUNT_WORDS 10
+#define HGNN_PACK_FLAG_BOUNDS 1 /* n outside [1, 32] or m > 72: the host batcher takes it          */
+#define HGNN_PACK_FLAG_INDEX 2  /* the edge-slot index error (hgnn_csr_batch_plan: HGNN_ERR_INDEX) */
+#define HGNN_PACK_FLAG_COO 4    /* an index >= n, or entries not strictly ascending row-major      */
+typedef struct hgnn_pack_view {
+    const int64_t* d_node_off;
+    const float* d_x;
+    const int64_t* d_adj_off;
+    const int32_t* d_adj_ij;
+    const float* d_adj_w;
+    const float* d_targets;
+    int64_t graphs;
+    int32_t f_in, reserved;
+} hgnn_pack_view;
+/* HGNN_ERR_ARG: null pointers, graphs <= 0, J < 1; HGNN_ERR_UNSUPPORTED: J > 3. */
+int hgnn_pack_count(const hgnn_pack_view* view, int J, int dual, int32_t* d_counts, void* stream);
+/* counts: host, bs x HGNN_PACK_COUNT_WORDS in batch order.  HGNN_ERR_INDEX if any record has
+ * HGNN_PACK_FLAG_INDEX, else HGNN_ERR_UNSUPPORTED if any has HGNN_PACK_FLAG_BOUNDS or _COO. */
+int hgnn_csr_layout_from_counts(int bs, const int32_t* counts, int f_in, int J, int dual,
+                                hgnn_csr_layout* layout);
+size_t hgnn_csr_batch_build_device_scratch_bytes(int bs);
+/* HGNN_ERR_ARG: a null pointer, bs <= 0, scratch_bytes too small, or a layout that is not one of
+ * (bs, view->f_in, J, dual); HGNN_ERR_UNSUPPORTED: J > 3. */
+int hgnn_csr_batch_build_device(const hgnn_pack_view* view, const int32_t* d_counts, const int32_t* d_idx,
+                                int bs, int J, int dual, const hgnn_csr_layout* layout, void* d_image,
+                                void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Device-resident training step (csrc/train.hip): the loss and optimizer of
  * train_with_mnb (scripts/train_mnb.py:41-91) with no host round trip.
  *
