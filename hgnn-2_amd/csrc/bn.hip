@@ -951,11 +951,10 @@ static void bn2_launch(const BnBwdArgs& a, hipStream_t s) {
     HGNN_KLAUNCH(k_bn_bwd_apply2<L>, dim3(t2), dim3(BN2_THREADS), 0, s, a);
 }
 
-// The launch sequences of the BN backward: part2s + apply2s (c = 4 / 8 / 16); part2 + apply2 (c = 64 / 128 / 256);
-// part4 -> apply4 on the atomic statistics (acc64), no k_bn_bwd_fin; part4 + fin (+ apply4); part + fin (+ apply).
-// bn_bwd_path is the one place that picks among them: the accumulator memset and the launches both follow it.
-enum class BnBwdPath { Narrow2s, Wide2, Part4Acc, Part4Fin, Scalar };
-static BnBwdPath bn_bwd_path(const BnBwdArgs& a, int apply, int tiles) {
+// The one place that picks among the launch sequences (kernels.h BnBwdPath): the accumulator memset and the
+// launches both follow it.
+BnBwdPath bn_bwd_variant(const BnBwdArgs& a, int apply) {
+    const int tiles = bn_bwd_tiles(a.cap_rows);
     // a padded dY stride is written by the scalar apply only
     if (!bn_vec4(a) || !(a.ldy == 0 || a.ldy == a.c)) return BnBwdPath::Scalar;
     // (c / 4 a power of two: the per-wave shuffle reduction pairs the lanes of one channel group)
@@ -971,7 +970,7 @@ static BnBwdPath bn_bwd_path(const BnBwdArgs& a, int apply, int tiles) {
 
 int launch_bn_backward(const BnBwdArgs& a, hipStream_t s, int apply) {
     const int tiles = bn_bwd_tiles(a.cap_rows);
-    const BnBwdPath path = bn_bwd_path(a, apply, tiles);
+    const BnBwdPath path = bn_bwd_variant(a, apply);
     // Part4Acc's apply4 zeroes the next half's accumulator region itself; every other path hands it over zeroed here
     if (a.acc64_zero && path != BnBwdPath::Part4Acc)
         HGNN_HOST_CHECK(hipMemsetAsync(a.acc64_zero, 0, (size_t)bn_acc_doubles(a.c) * sizeof(double), s));
@@ -1216,13 +1215,15 @@ static void allow_ro_lds(K* kernel, size_t lds) {
 }
 
 bool readout_row_fits(const ReadoutAggArgs& ra, const DwDenseArgs* dw) {
-    if (ra.jt > 8) return false;
+    if (ra.jt > 7) return false;  // entries of 8 floats: the column and up to 7 coefficients
     if ((ra.g_out || ra.p_out) && readout_agg_bwd_lds(ra) > RO_LDS_CAP) return false;
     return !dw || dw_readout_lds(*dw) <= RO_LDS_CAP;
 }
 
 int launch_readout_agg_bwd(const ReadoutAggArgs& a, hipStream_t s) {
-    if (a.jt > 8 || (!a.g_out && !a.p_out)) return a.jt > 8 ? HGNN_ERR_UNSUPPORTED : 0;
+    // k_readout_agg_bwd reads floats [1, 1 + jt) of a G entry: 1 + jt <= stride <= 8
+    if (a.jt > 7 || (a.g_out && 1 + a.jt > a.g.stride)) return HGNN_ERR_UNSUPPORTED;
+    if (!a.g_out && !a.p_out) return 0;
     const size_t lds = readout_agg_bwd_lds(a);
     if (lds > RO_LDS_CAP) return HGNN_ERR_UNSUPPORTED;
     allow_ro_lds(k_readout_agg_bwd, lds);

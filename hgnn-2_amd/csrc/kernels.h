@@ -385,8 +385,12 @@ struct BnBwdArgs {
     const float* w;
     int relu_from;
     int training;
-    float* part;           // scratch [tiles][c][2]
-    float* sums;           // scratch [c][2] + [2]
+    // scratch: the statistics partials, one float4 {sum g, sum g h, sum dz h, sum dz} per (channel, tile).  The
+    // part4 / scalar paths index it by bn_bwd_part_index over bn_bwd_tiles(cap_rows) 64-row tiles (channel-major
+    // [c][tiles][4]); the two-launch forms by 256-row tiles ([ceil(cap_rows / 256)][c][4]).  The buffer must hold
+    // the larger: 4 c bn_bwd_tiles(cap_rows) floats, 16-byte aligned
+    float* part;
+    float* sums;           // scratch [c][4]: the four statistics per channel (k_bn_bwd_fin), 16-byte aligned
     float* dy;             // out [rows][ldy] (ldy = 0: c; ldy > c only on the scalar path, c % 4 != 0)
     int ldy;
     float* dw;             // scalar out
@@ -404,6 +408,12 @@ constexpr int BN_ACC_COPIES = 8, BN_ACC_STATS = 4;
 __host__ __device__ inline long long bn_acc_doubles(int c) { return (long long)BN_ACC_COPIES * BN_ACC_STATS * c; }
 // apply = 0: only the statistics (part + fin)
 int launch_bn_backward(const BnBwdArgs& a, hipStream_t s, int apply = 1);
+// The launch sequences of the BN backward: part2s + apply2s (c = 4 / 8 / 16); part2 + apply2 (c = 64 / 128 / 256);
+// part4 -> apply4 on the atomic statistics (acc64), no k_bn_bwd_fin; part4 + fin (+ apply4); part + fin (+ apply).
+// bn_bwd_variant is the one place that picks among them under the process's switches: launch_bn_backward's
+// accumulator memset and launches both follow it (the values are those of HGNN_BN_BWD_* in the header)
+enum class BnBwdPath : int { Narrow2s = 0, Wide2 = 1, Part4Acc = 2, Part4Fin = 3, Scalar = 4 };
+BnBwdPath bn_bwd_variant(const BnBwdArgs& a, int apply);
 __host__ __device__ inline int bn_bwd_tiles(int cap_rows) { return (cap_rows + 63) / 64; }
 // k_bn_bwd_part / part4 -> k_bn_bwd_fin partials: float4 {sum g, sum g h, sum dz h, sum dz} per (channel,
 // 64-row tile), channel-major [c][tiles] so the fin's per-channel loads are contiguous over the tiles

@@ -136,6 +136,36 @@ class ProbeAggBwd(ctypes.Structure):
                                               "accumulate")]
 
 
+class ProbeBnFinalize(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("acc", "part", "count", "mean", "std", "run_mean", "run_std")] + \
+               [(n, ctypes.c_int32) for n in ("tiles", "c", "training", "reserved")]
+
+
+# hgnn_probe_bn_backward_args.path (HGNN_BN_BWD_*)
+BN_BWD_PATHS = ("narrow2s", "wide2", "part4acc", "part4fin", "scalar")
+
+
+class ProbeBnBackward(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("y", "dz", "total_rows", "mean", "std", "w", "part", "sums", "dy", "dw",
+                                                "db", "dbpart", "acc64", "acc64_zero")] + \
+               [(n, ctypes.c_int32) for n in ("cap_rows", "c", "relu_from", "training", "ldy", "apply", "path",
+                                              "reserved")]
+
+
+class ProbeReadoutAgg(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("dout", "fcw", "node_off", "edge_off")] + \
+               [("g", ProbeList), ("g_total", ctypes.c_void_p), ("g_out", ctypes.c_void_p), ("p", ProbeList),
+                ("p_total", ctypes.c_void_p), ("p_out", ctypes.c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ("dim_out", "k", "jt", "cg", "cp", "bs", "g_cap", "g_acc", "p_cap",
+                                              "p_acc")]
+
+
+class ProbeDwDense(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("dA", "xp", "xdense", "pmean", "pstd", "pw", "pb", "dout", "fcw",
+                                                "node_off", "dW")] + \
+               [(n, ctypes.c_int32) for n in ("lda", "f", "jt", "dim_out", "kfc", "bs", "nmax", "accumulate")]
+
+
 _lib = None
 
 _VP = ctypes.c_void_p
@@ -253,6 +283,16 @@ SIGNATURES = {
     "hgnn_probe_unpack_nodes": ([_VP, _I, _I, _I, _VP, _VP, _VP], _I),
     "hgnn_probe_agg_fwd": ([ctypes.POINTER(ProbeAggFwd), _VP], _I),
     "hgnn_probe_agg_bwd": ([ctypes.POINTER(ProbeAggBwd), ctypes.POINTER(ProbeAggBwd), _I, _VP], _I),
+    "hgnn_probe_bn_finalize": ([ctypes.POINTER(ProbeBnFinalize), _VP], _I),
+    "hgnn_probe_bn_backward": ([ctypes.POINTER(ProbeBnBackward), _VP], _I),
+    "hgnn_probe_readout_fwd": ([_VP, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP], _I),
+    "hgnn_probe_readout_bwd_da": ([_VP, _VP, _I, _I, _VP, _VP, _I, _I, _VP, _VP], _I),
+    "hgnn_probe_readout_bwd_scratch_bytes": ([_I, _I], ctypes.c_size_t),
+    "hgnn_probe_readout_bwd_params": ([_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP], _I),
+    "hgnn_probe_readout_agg_bwd": ([ctypes.POINTER(ProbeReadoutAgg), _VP], _I),
+    "hgnn_probe_dw_dense": ([ctypes.POINTER(ProbeDwDense), _VP], _I),
+    "hgnn_probe_dw_readout": ([ctypes.POINTER(ProbeDwDense), _VP], _I),
+    "hgnn_probe_readout_row_fits": ([ctypes.POINTER(ProbeReadoutAgg), ctypes.POINTER(ProbeDwDense)], _I),
 }
 
 

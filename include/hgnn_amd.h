@@ -817,6 +817,109 @@ typedef struct hgnn_probe_agg_bwd_args {
 } hgnn_probe_agg_bwd_args;
 int hgnn_probe_agg_bwd(const hgnn_probe_agg_bwd_args* a, const hgnn_probe_agg_bwd_args* b, int pair, void* stream);
 
+/* ---- The dense side outside the GEMMs (csrc/bn.hip, csrc/dwdense.hip): the BN finalize and backward, the readout
+ * launchers and the dense operator gradient, under the same rules (csrc/probe_dense.hip).  Every scratch buffer is
+ * the caller's. */
+
+/* csrc/kernels.h BnFwdArgs (launch_bn_finalize).  Exactly one of acc ([8][2][c] fp64: sum y, sum y^2 per copy) and
+ * part ([ceil(count / 64)][c][3]: count, mean, M2 per 64-row tile) in training mode; eval mode (training = 0)
+ * copies run_mean / run_std (required then).  momentum is 0.1, as the executor's. */
+typedef struct hgnn_probe_bn_finalize_args {
+    const double* acc;
+    const float* part;
+    const int32_t* count;    /* device: the real rows */
+    float* mean;             /* (c) */
+    float* std;              /* (c) */
+    float* run_mean;         /* optional pair, read and updated in place */
+    float* run_std;
+    int32_t tiles, c, training, reserved;
+} hgnn_probe_bn_finalize_args;
+int hgnn_probe_bn_finalize(const hgnn_probe_bn_finalize_args* p, void* stream);
+
+/* The launch sequence launch_bn_backward takes (csrc/kernels.h BnBwdPath, bn_bwd_variant). */
+enum {
+    HGNN_BN_BWD_NARROW2S = 0,  /* k_bn_bwd_part2s + apply2s */
+    HGNN_BN_BWD_WIDE2 = 1,     /* k_bn_bwd_part2 + apply2 */
+    HGNN_BN_BWD_PART4ACC = 2,  /* k_bn_bwd_part4 (fp64 atomics) + apply4 */
+    HGNN_BN_BWD_PART4FIN = 3,  /* k_bn_bwd_part4 + fin (+ apply4) */
+    HGNN_BN_BWD_SCALAR = 4     /* k_bn_bwd_part + fin (+ apply) */
+};
+
+/* csrc/kernels.h BnBwdArgs (launch_bn_backward) and `apply` (0: only the statistics into sums).  y, dz
+ * [rows][c] (no kernel reads a row >= *total_rows), part: 4 c ceil(cap_rows / 64) floats, sums: 4 c floats, both
+ * 16-byte aligned; dy [rows][ldy] (ldy = 0: c); dbpart optional [ceil(cap_rows / 64)][c]; acc64 / acc64_zero
+ * optional, 32 c doubles each.  path (written on the host): the HGNN_BN_BWD_* sequence the launcher chose. */
+typedef struct hgnn_probe_bn_backward_args {
+    const float* y;
+    const float* dz;
+    const int32_t* total_rows;
+    const float* mean;
+    const float* std;
+    const float* w;
+    float* part;
+    float* sums;
+    float* dy;
+    float* dw;
+    float* db;
+    float* dbpart;
+    double* acc64;
+    double* acc64_zero;
+    int32_t cap_rows, c, relu_from, training, ldy, apply;
+    int32_t path, reserved;
+} hgnn_probe_bn_backward_args;
+int hgnn_probe_bn_backward(hgnn_probe_bn_backward_args* p, void* stream);
+
+/* launch_readout_fwd: a [rows][k], node_off (bs + 1), fcw (dim_out, k), fcb (dim_out) -> colsum (bs, k),
+ * out (bs, dim_out). */
+int hgnn_probe_readout_fwd(const float* d_a, int k, const int32_t* d_node_off, int bs, int nmax, const float* d_fcw,
+                           const float* d_fcb, int dim_out, float* d_colsum, float* d_out, void* stream);
+/* launch_readout_bwd_da: da [rows][k], row r of graph b = dout[b] . fcw. */
+int hgnn_probe_readout_bwd_da(const float* d_dout, const int32_t* d_node_off, int bs, int cap_rows,
+                              const int32_t* d_total_rows, const float* d_fcw, int dim_out, int k, float* d_da,
+                              void* stream);
+/* launch_readout_bwd_params: dfcw (dim_out, k), dfcb (dim_out); scratch of hgnn_probe_readout_bwd_scratch_bytes. */
+size_t hgnn_probe_readout_bwd_scratch_bytes(int dim_out, int k);
+int hgnn_probe_readout_bwd_params(const float* d_dout, const float* d_colsum, int bs, int nmax, int dim_out, int k,
+                                  float* d_dfcw, float* d_dfcb, void* scratch, void* stream);
+
+/* csrc/kernels.h ReadoutAggArgs (launch_readout_agg_bwd, readout_row_fits).  g: the S_WT list (node rows, jt
+ * coefficients per entry), p: the S_PE list (edge rows, pm and pd); g_cap / p_cap: bs times the most rows a graph
+ * may hold (the kernel's LDS is sized from them). */
+typedef struct hgnn_probe_readout_agg_args {
+    const float* dout;
+    const float* fcw;
+    const int32_t* node_off;
+    const int32_t* edge_off;
+    hgnn_probe_list g;
+    const int32_t* g_total;
+    float* g_out;            /* NULL: no G gather */
+    hgnn_probe_list p;
+    const int32_t* p_total;
+    float* p_out;            /* NULL: no P gather */
+    int32_t dim_out, k, jt, cg, cp, bs, g_cap, g_acc, p_cap, p_acc;
+} hgnn_probe_readout_agg_args;
+int hgnn_probe_readout_agg_bwd(const hgnn_probe_readout_agg_args* p, void* stream);
+
+/* csrc/kernels.h DwDenseArgs (launch_dw_dense, launch_dw_readout).  dW (bs, nmax, nmax, jt). */
+typedef struct hgnn_probe_dw_dense_args {
+    const float* dA;         /* [rows][lda] (launch_dw_dense) */
+    const float* xp;         /* [rows][f], or */
+    const float* xdense;     /* (bs, f, nmax) */
+    const float* pmean;      /* optional BN of the producer of xp: (f), (f), scalar, scalar */
+    const float* pstd;
+    const float* pw;
+    const float* pb;
+    const float* dout;       /* optional (bs, dim_out): readout mode */
+    const float* fcw;        /* (dim_out, kfc) */
+    const int32_t* node_off;
+    float* dW;
+    int32_t lda, f, jt, dim_out, kfc, bs, nmax, accumulate;
+} hgnn_probe_dw_dense_args;
+int hgnn_probe_dw_dense(const hgnn_probe_dw_dense_args* p, void* stream);
+int hgnn_probe_dw_readout(const hgnn_probe_dw_dense_args* p, void* stream);
+/* readout_row_fits(ra, dw): 1 when the readout-row backward fits its LDS (dw optional). */
+int hgnn_probe_readout_row_fits(const hgnn_probe_readout_agg_args* ra, const hgnn_probe_dw_dense_args* dw);
+
 #ifdef __cplusplus
 }
 #endif
