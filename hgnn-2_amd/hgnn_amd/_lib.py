@@ -249,6 +249,7 @@ SIGNATURES = {
     "hgnn_csr_batch_build_device_scratch_bytes": ([_I], ctypes.c_size_t),
     "hgnn_csr_batch_build_device": ([ctypes.POINTER(PackView), _VP, _VP, _I, _I, _I, ctypes.POINTER(CsrLayout), _VP,
                                      _VP, ctypes.c_size_t, _VP], _I),
+    "hgnn_pack_ccn_chunk": ([ctypes.POINTER(PackView), _I, _VP, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP], _I),
     "hgnn_net_backward_ex": ([ctypes.POINTER(NetConfig), ctypes.POINTER(NetInputs), ctypes.POINTER(CsrBatch), _VP, _VP,
                               _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I], _I),
     "hgnn_net_forward_csr": ([ctypes.POINTER(NetConfig), ctypes.POINTER(CsrBatch), _VP, _VP, _VP, _VP, _VP], _I),

@@ -16,6 +16,8 @@ files through rdkit (preprocessing/preprocessing.py:174-275).  Here:
   reference's dense 11-tuple through functions.batching.prepare_batch.
 * DevicePack (GraphPack.to_device) -- the pack resident on the GPU; the same CsrBatch images built there
   by the device batcher (csrc/batcher.hip), with no host work per graph.
+* GraphPack.ccn_chunks / DevicePack.ccn_chunk -- the CCN drivers' padded (X, A + I, n_batch, y) chunks, gathered
+  in numpy or built on the GPU (csrc/ccn_pack.hip).
 * prepare_experiment_sets -- the reference split, same sizes and order.
 * read_xyz / molecule_targets / atom_one_hot -- the QM9 `.xyz` reader: header
   properties, atoms (with the `*^` exponent form), frequencies and SMILES; the
@@ -157,9 +159,69 @@ class GraphPack:
             targets = torch.tensor([float(t[task]) for _, _, t in graphs], dtype=torch.float32)
             yield CsrBatch([(x, a) for x, a, _ in graphs], J=J, dual=dual, targets=targets, device=device)
 
+    def ccn_chunks(self, idx, chunk, task, device="cpu"):
+        """Yield (X (G, nmax, f), A + I (G, nmax, nmax), n_batch (G,) int64, y (G, 1)) per `chunk` consecutive
+        indices of `idx`, each chunk padded to its own largest graph: what CcnTrainStep._chunks makes of the
+        reference's 7-tuples (scripts/train_ccn.py:35-37), gathered from the mapped arrays with no loop over
+        graphs or entries."""
+        idx = np.asarray(list(idx), dtype=np.int64)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(self)):
+            raise IndexError(f"hgnn_amd: graph index outside the pack of {len(self)}")
+        node_off, adj_off = np.asarray(self.node_off), np.asarray(self.adj_off)
+        f = int(self.x.shape[1])
+        for c0 in range(0, len(idx), chunk):
+            part = idx[c0:c0 + chunk]
+            G = len(part)
+            n = node_off[part + 1] - node_off[part]
+            cnt = adj_off[part + 1] - adj_off[part]
+            nmax = int(n.max())
+            # per node / per entry: its slot in the chunk and its place in the pack
+            slot_n = np.repeat(np.arange(G), n)
+            local = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            slot_e = np.repeat(np.arange(G), cnt)
+            src_e = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(adj_off[part], cnt)
+            X = np.zeros((G, nmax, f), np.float32)
+            X[slot_n, local] = self.x[np.repeat(node_off[part], n) + local]
+            A = np.zeros((G, nmax, nmax), np.float32)
+            ij = self.adj_ij[src_e]
+            A[slot_e, ij[:, 0], ij[:, 1]] = self.adj_w[src_e]
+            A[slot_n, local, local] += np.float32(1.0)  # + torch.eye(n)
+            y = np.asarray(self.targets[part, task], dtype=np.float32).reshape(G, 1)
+            yield tuple(torch.from_numpy(t).to(device) for t in (X, A, n.astype(np.int64), y))
+
     def to_device(self, J=1, dual=True, device="cuda"):
-        """DevicePack(self, J, dual, device): the pack resident on the GPU, batches built there."""
+        """DevicePack(self, J, dual, device): the pack resident on the GPU, batches built there.  J=None: a pack
+        for the CCN only (ccn_chunk; no CSR batches)."""
         return DevicePack(self, J=J, dual=dual, device=device)
+
+
+def coo_first_bad_graph(node_off, adj_off, adj_ij):
+    """The first graph whose adjacency entries are not all in [0, n)^2 and strictly ascending row-major, or
+    -1: hgnn_pack_count's HGNN_PACK_FLAG_COO, on the host over the whole pack at once."""
+    node_off, adj_off = np.asarray(node_off, dtype=np.int64), np.asarray(adj_off, dtype=np.int64)
+    ij = np.asarray(adj_ij, dtype=np.int64).reshape(-1, 2)
+    n, cnt = np.diff(node_off), np.diff(adj_off)
+    gid = np.repeat(np.arange(len(n)), cnt)
+    ne = n[gid]
+    i, j = ij[:, 0], ij[:, 1]
+    bad = (i < 0) | (i >= ne) | (j < 0) | (j >= ne)
+    key = i * ne + j  # row-major rank within the graph (where in range)
+    if len(key) > 1:
+        bad[1:] |= (gid[1:] == gid[:-1]) & (key[1:] <= key[:-1])
+    hit = np.nonzero(bad)[0]
+    return int(gid[hit[0]]) if len(hit) else -1
+
+
+def _coo_error(pack, g):
+    return RuntimeError(f"hgnn_amd: graph {g} of {pack.path}: adjacency entries out of range "
+                        "or not in strictly ascending row-major order")
+
+
+def check_coo(pack):
+    """Raise the RuntimeError DevicePack raises for a malformed adjacency; needs no GPU."""
+    g = coo_first_bad_graph(pack.node_off, pack.adj_off, pack.adj_ij)
+    if g >= 0:
+        raise _coo_error(pack, g)
 
 
 class DevicePack:
@@ -174,6 +236,11 @@ class DevicePack:
     The device builder takes graphs of at most 32 nodes and 72 edge slots and J <= 3; a batch with a larger
     graph, and every batch at J > 3, is built by the host batcher (pack.batches).  A batch with a graph whose
     edge-slot construction fails raises IndexError as CsrBatch does, when that batch is asked for.
+
+    ccn_chunk(idx, task) enqueues hgnn_pack_ccn_chunk (csrc/ccn_pack.hip): the padded (X, A + I, n_batch, y) chunk
+    of the CCN drivers, for graphs of any size.  J=None makes a pack for the CCN only: nothing is counted on the
+    device, the adjacency entries are validated on the host instead (check_coo), and batch() raises.  The kernel
+    reports a graph it had to leave out (an empty slot) in one device error word; check() reads it.
     """
 
     def __init__(self, pack, J=1, dual=True, device="cuda"):
@@ -185,7 +252,7 @@ class DevicePack:
             dev = torch.device("cuda", torch.cuda.current_device())
         if len(pack) == 0:
             raise RuntimeError("hgnn_amd: DevicePack: the pack holds no graphs")
-        self.pack, self.J, self.dual, self.device = pack, int(J), bool(dual), dev
+        self.pack, self.J, self.dual, self.device = pack, None if J is None else int(J), bool(dual), dev
         self.f_in = int(pack.x.shape[1])
         host = {k: np.ascontiguousarray(getattr(pack, k)) for k in GraphPack.FILES}
         for off, total in ((host["node_off"], len(host["x"])), (host["adj_off"], len(host["adj_w"]))):
@@ -199,8 +266,15 @@ class DevicePack:
         self.targets = self._arrays["targets"]
         a = self._arrays
         self._view = L.PackView(*[a[k].data_ptr() for k in GraphPack.FILES], len(pack), self.f_in, 0)
+        self.n_targets = int(host["targets"].shape[1])
+        self._n = np.diff(host["node_off"])  # nodes per graph: sizes a CCN chunk on the host
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)  # hgnn_pack_ccn_chunk's error word
         self.counts = None  # (graphs, 10) int32 records on the host; None at J > 3 (the host batcher builds all)
-        if self.J <= 3:
+        if self.J is None:
+            g = coo_first_bad_graph(host["node_off"], host["adj_off"], host["adj_ij"])
+            if g >= 0:
+                raise _coo_error(pack, g)
+        elif self.J <= 3:
             self._counts = torch.empty(len(pack), L.PACK_COUNT_WORDS, dtype=torch.int32, device=dev)
             with torch.cuda.device(dev):
                 L.check(L.lib().hgnn_pack_count(ctypes.byref(self._view), self.J, int(self.dual),
@@ -219,6 +293,9 @@ class DevicePack:
         the device on the current stream."""
         from . import _lib as L
         from .csr import CsrBatch
+        if self.J is None:
+            raise RuntimeError("hgnn_amd: DevicePack(J=None) is a pack for the CCN only (ccn_chunk); CSR batches "
+                               "need the J of the model")
         idx = [int(i) for i in idx]
         bs = len(idx)
         if bs == 0:
@@ -256,6 +333,51 @@ class DevicePack:
         idx = list(idx)
         for b0 in range(0, len(idx), batch_size):
             yield self.batch(idx[b0:b0 + batch_size], task)
+
+    def ccn_chunk(self, idx, task, nmax=None):
+        """(X (G, nmax, f), A + I (G, nmax, nmax), n_batch (G,) int64, y (G, 1)) of the graphs `idx` (in that
+        order; repeats allowed) with targets[idx, task], built on the device on the current stream: the chunk
+        GraphPack.ccn_chunks and CcnTrainStep._chunks build on the host, bit for bit.  nmax: the chunk's largest
+        graph, or a larger padding."""
+        from . import _lib as L
+        idx = [int(i) for i in idx]
+        G = len(idx)
+        if G == 0:
+            raise RuntimeError("hgnn_amd: empty chunk")
+        if min(idx) < 0 or max(idx) >= len(self.pack):
+            raise IndexError(f"hgnn_amd: graph index outside the pack of {len(self.pack)}")
+        big = int(self._n[np.asarray(idx, dtype=np.int64)].max())
+        if nmax is None:
+            nmax = big
+        elif int(nmax) < big:
+            raise RuntimeError(f"hgnn_amd: nmax = {nmax}, but the chunk holds a graph of {big} nodes")
+        nmax = int(nmax)
+        dev = self.device
+        with torch.cuda.device(dev):
+            X = torch.empty(G, nmax, self.f_in, dtype=torch.float32, device=dev)
+            A = torch.empty(G, nmax, nmax, dtype=torch.float32, device=dev)
+            nb = torch.empty(G, dtype=torch.int64, device=dev)
+            y = torch.empty(G, 1, dtype=torch.float32, device=dev)
+            d_idx = torch.tensor(idx, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+            L.check(L.lib().hgnn_pack_ccn_chunk(ctypes.byref(self._view), self.n_targets, L.ptr(d_idx), G, nmax,
+                                                int(task), L.ptr(X), L.ptr(A), L.ptr(nb), L.ptr(y),
+                                                L.ptr(self._err), L.stream_handle(dev)), "hgnn_pack_ccn_chunk")
+        return X, A, nb, y
+
+    def ccn_chunks(self, idx, chunk, task):
+        """One ccn_chunk per `chunk` consecutive indices of `idx`, as GraphPack.ccn_chunks yields them."""
+        idx = list(idx)
+        for c0 in range(0, len(idx), chunk):
+            yield self.ccn_chunk(idx[c0:c0 + chunk], task)
+
+    def check(self):
+        """Raise if a ccn_chunk since the last check left a graph out as an empty slot (one host read)."""
+        bits = int(self._err.item())
+        if bits:
+            self._err.zero_()
+            raise RuntimeError("hgnn_amd: DevicePack.ccn_chunk left a graph out (index outside the pack, more nodes "
+                               "than nmax, or adjacency entries out of range or out of order): the device copy of "
+                               f"{self.pack.path} is corrupt")
 
 
 # ---------------------------------------------------------------- QM9 .xyz

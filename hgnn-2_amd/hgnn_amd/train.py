@@ -670,32 +670,57 @@ class CcnTrainStep(_Optimizer):
                 y[b, 0] = d[2][task]
             yield X.to(dev), A.to(dev), nb.to(dev), y.to(dev)
 
+    def _epoch_chunks(self, data, task, chunk):
+        """The padded device chunks of one epoch, graphs in order 0 .. len - 1 (train_ccn.py's for i in range(n)).
+        data: the reference's list of 7-tuples (_chunks), a hgnn_amd.dataset.GraphPack (gathered on the host,
+        vectorised) or a hgnn_amd.dataset.DevicePack on the model's device (built there by hgnn_pack_ccn_chunk,
+        no host work per graph) -- the same bytes from all three."""
+        from .dataset import DevicePack, GraphPack
+        dev = self.params[0].device
+        if isinstance(data, DevicePack):
+            if data.device != dev:
+                raise RuntimeError(f"hgnn_amd: DevicePack on {data.device}, model on {dev}")
+            return data.ccn_chunks(range(len(data)), chunk, task)
+        if isinstance(data, GraphPack):
+            return data.ccn_chunks(range(len(data)), chunk, task, device=dev)
+        return self._chunks(data, task, chunk)
+
+    @staticmethod
+    def _check_pack(data):
+        # after the read that ends the epoch: the stream is drained, the error word costs no extra wait
+        from .dataset import DevicePack
+        if isinstance(data, DevicePack):
+            data.check()
+
     def train_epoch(self, data, task, chunk=1024):
         """train_ccn(net, data, task, ...) (scripts/train_ccn.py:24-73): one step per graph in list order, new
         meters; returns (losses.val, error.val), read once at the end.  Classification: targets[task] is the
-        class index, n_outputs >= 2, and error.val is the 0.0 the reference's untouched meter returns."""
+        class index, n_outputs >= 2, and error.val is the 0.0 the reference's untouched meter returns.
+        data: a list of instances, a GraphPack or a DevicePack (_epoch_chunks)."""
         if self.spec.n_out != 1 and not self.classification:
             raise RuntimeError("hgnn_amd: train_epoch takes one target per graph (targets[task].view(1))")
         self.reset_running()
-        for X, A, nb, y in self._chunks(data, task, chunk):
+        for X, A, nb, y in self._epoch_chunks(data, task, chunk):
             self.step(X, A, nb, y)
         s = self.stats.tolist()
+        self._check_pack(data)
         return (s[2], 0.0) if self.classification else (s[2], s[3])
 
     def eval_epoch(self, data, task, chunk=1024, accuracy=False):
         """test_ccn(ccn, data, task, ...) (scripts/test_ccn.py:23-67): (losses.avg, error.avg) over the list;
         the chunks' means weighted by their graph counts, as AverageMeter.update(v, 1) per graph does.
         Classification: (losses.avg, 0.0) as the reference returns; accuracy=True adds the accuracy as a third
-        value."""
+        value.  data: as train_epoch takes it."""
         if accuracy and not self.classification:
             raise RuntimeError("hgnn_amd: eval_epoch(accuracy=True) needs a classification step")
         if self.spec.n_out != 1 and not self.classification:
             raise RuntimeError("hgnn_amd: eval_epoch takes one target per graph (targets[task].view(1))")
         acc = None
-        for X, A, nb, y in self._chunks(data, task, chunk):
+        for X, A, nb, y in self._epoch_chunks(data, task, chunk):
             r = self.evaluate(X, A, nb, y).double() * X.shape[0]
             acc = r if acc is None else acc + r
         if acc is None:
             return (0.0, 0.0, 0.0) if accuracy else (0.0, 0.0)
         s = (acc / len(data)).tolist()
+        self._check_pack(data)
         return (s[0], s[1], s[2]) if accuracy else (s[0], s[1])

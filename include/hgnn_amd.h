@@ -326,6 +326,23 @@ int hgnn_csr_batch_build_device(const hgnn_pack_view* view, const int32_t* d_cou
                                 int bs, int J, int dual, const hgnn_csr_layout* layout, void* d_image,
                                 void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* CCN chunk from the resident pack (csrc/ccn_pack.hip): the padded batch hgnn_ccn_forward and the CCN
+ * training loops take, as hgnn_amd.train.CcnTrainStep._chunks assembles it on the host
+ * (scripts/train_ccn.py:35-37 plus padding) -- bit for bit.  One enqueue, no host synchronisation.  For
+ * b < G and g = d_idx[b] (any order, repeats allowed):
+ *   d_X[b]       (nmax, f_in)  rows < n_g from the pack, everything else 0
+ *   d_adj[b]     (nmax, nmax)  A + I in fp32: the stored weight off the diagonal, w + 1.0f on it (w = 0 where
+ *                              no entry is stored), 0 at every row or column >= n_g
+ *   d_n_batch[b] = n_g,  d_y[b] = targets[g * n_targets + task]   (targets: (graphs, n_targets) fp32)
+ * Every element of the four outputs is written; they may be uninitialised.  Nothing else is written, whatever
+ * the pack holds: a slot whose g is outside [0, graphs), whose n_g > nmax, or whose entries are not all in
+ * [0, n_g)^2 and strictly ascending row-major becomes the empty slot the CCN kernels skip (all zero,
+ * n_batch = 0, y = 0), and bit 1 is ORed into *d_err (int32, may be null).  Any n_g <= nmax is taken.
+ * HGNN_ERR_ARG: a null pointer (view members and d_targets included), G <= 0, nmax <= 0, task outside
+ * [0, n_targets); HGNN_ERR_UNSUPPORTED: nmax * (nmax + 1) or nmax * f_in >= 2^31. */
+int hgnn_pack_ccn_chunk(const hgnn_pack_view* view, int n_targets, const int32_t* d_idx, int G, int nmax, int task,
+                        float* d_X, float* d_adj, int64_t* d_n_batch, float* d_y, int32_t* d_err, void* stream);
+
 /* ------------------------------------------------------------------------
  * Device-resident training step (csrc/train.hip): the loss and optimizer of
  * train_with_mnb (scripts/train_mnb.py:41-91) with no host round trip.
