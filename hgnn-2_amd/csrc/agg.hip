@@ -431,6 +431,177 @@ __global__ void __launch_bounds__(AGG_NT) k_agg_fwd_rpw(AggFwdArgs a) {
     }
 }
 
+// ---- Narrow rows (c <= AGG_NLPR channels: layer 0 of the line-graph networks, every layer of GNN_simple).  One
+// row per wave leaves 1 to 8 of the 64 lanes with work and makes a row cost a wave's three dependent round trips.
+// Here a group of AGG_NLPR lanes serves one row (lane i of the group: channel i) and a wave takes 64 / AGG_NLPR
+// consecutive rows: one lane-parallel load fetches all the groups' row infos, the next all their entry chunks (lane
+// i of a group: entry i of the chunk), then the gathers of all groups go out together; an entry is broadcast
+// within its group by __shfl.  The chunk loop's trip count is the wave's longest row; no per-lane condition
+// guards a load (addresses are clamped to a live entry / row / channel and the value is selected afterwards).
+// Every output element is the same fmaf chain in list order as in k_agg_fwd / agg_bwd_g / agg_bwd_p.
+// AGG_NARROW=0 at build time (A/B) leaves these rows to the one-row-per-wave kernels.
+#ifndef AGG_NARROW
+#define AGG_NARROW 1
+#endif
+constexpr int AGG_NLPR = 8, AGG_NGPW = 64 / AGG_NLPR, AGG_NU = 4;
+
+__device__ __forceinline__ RowInfo row_info_lane(const RowInfo* rows, int r) {
+    const int2 v = *reinterpret_cast<const int2*>(reinterpret_cast<const int*>(rows) + 2 * (long long)r);
+    return RowInfo{v.x, v.y};
+}
+
+// One list of the wave's rows, per lane: cnt the group's row count; base its first entry, or -- for an empty row --
+// the first entry of a row of the wave that has one, so a clamped entry address is always a live entry; wmax the
+// wave's longest row (uniform; 0: no row of the wave has an entry and nothing of the list is read).
+struct NarrowList {
+    int base, cnt, wmax;
+    __device__ __forceinline__ void init(RowInfo ri) {
+        cnt = ri.count;
+        const unsigned long long m = __ballot(ri.count > 0);
+        const int fs = __shfl(ri.start, m ? __ffsll(m) - 1 : 0, 64);
+        base = ri.count > 0 ? ri.start : fs;
+        int w = max(ri.count, 0);
+#pragma unroll
+        for (int o = AGG_NLPR; o < 64; o <<= 1) w = max(w, __shfl_xor(w, o, 64));
+        wmax = __builtin_amdgcn_readfirstlane(w);
+    }
+    // the entry this lane holds of the chunk at e0 (i: lane of the group): its index, clamped to the row's last
+    // entry, and whether it is one of the row's
+    __device__ __forceinline__ long long at(int e0, int i, bool& live) const {
+        live = e0 + i < cnt;
+        return (long long)base + min(e0 + i, max(cnt - 1, 0));
+    }
+};
+
+__device__ __forceinline__ float grp_bcast(float v, int src) { return __shfl(v, src, 64); }
+__device__ __forceinline__ float f4_at(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
+// (HG / HP: the launch has a G / P part; a.cg, a.cp <= AGG_NLPR, j0 = 0)
+template <int JT, bool HG, bool HP>
+__global__ void __launch_bounds__(AGG_NT) k_agg_fwd_narrow(AggFwdArgs a) {
+    WaveStamp stamp(a.stamps);
+    const int r0 = __builtin_amdgcn_readfirstlane((blockIdx.x * AGG_WV + (threadIdx.x >> 6)) * AGG_NGPW);
+    const int lane = threadIdx.x & 63, i = lane & (AGG_NLPR - 1), g0 = lane & ~(AGG_NLPR - 1);
+    const int total = *a.total_rows;
+    if (r0 >= total) return;
+    const int r = r0 + (lane >> 3);
+    const int rc = min(r, total - 1);  // (rows past the total: a live row, never stored)
+    NarrowList gl{0, 0, 0}, pl{0, 0, 0};
+    {
+        RowInfo rg{0, 0}, rp{0, 0};
+        if constexpr (HG) rg = row_info_lane(a.g.rows, rc);
+        if constexpr (HP) rp = row_info_lane(a.p.rows, rc);
+        if constexpr (HG) gl.init(rg);
+        if constexpr (HP) pl.init(rp);
+    }
+    // BN constants of the lane's channel (clamped: lanes past the width hold a copy, never stored)
+    const int ig = min(i, max(a.cg - 1, 0)), ip = min(i, max(a.cp - 1, 0));
+    const bool gbn = HG && a.gbn.mean != nullptr, pbn = HP && a.pbn.mean != nullptr;
+    float gmu = 0.f, gsc = 1.f, gb = 0.f, pmu = 0.f, psc = 1.f, pb = 0.f;
+    if (gbn) gmu = a.gbn.mean[ig], gsc = bn_scale(*a.gbn.w, a.gbn.std[ig]), gb = *a.gbn.b;
+    if (pbn) pmu = a.pbn.mean[ip], psc = bn_scale(*a.pbn.w, a.pbn.std[ip]), pb = *a.pbn.b;
+    const int stride = a.g.stride;
+    float acc[JT], am = 0.f, ad = 0.f;
+#pragma unroll
+    for (int j = 0; j < JT; ++j) acc[j] = 0.f;
+    const int nmax = max(gl.wmax, pl.wmax);
+    for (int e0 = 0; e0 < nmax; e0 += AGG_NLPR) {
+        const bool gon = HG && e0 < gl.wmax, pon = HP && e0 < pl.wmax;  // uniform
+        float4 mg = make_float4(0.f, 0.f, 0.f, 0.f), mp = mg, mx4 = mg;
+        if (gon) {
+            bool live;
+            const float* q = a.g.entries + gl.at(e0, i, live) * stride;
+            mg = *reinterpret_cast<const float4*>(q);
+            if constexpr (JT > 3) mx4 = *reinterpret_cast<const float4*>(q + 4);
+            if (!live) {
+                mg.y = mg.z = mg.w = 0.f;
+                mx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        if (pon) {
+            bool live;
+            mp = *reinterpret_cast<const float4*>(a.p.entries + pl.at(e0, i, live) * 4);
+            if (!live) mp.y = mp.z = 0.f;
+        }
+        const int nn = min(AGG_NLPR, nmax - e0);
+        for (int e = 0; e < nn; e += AGG_NU) {
+            float xg[AGG_NU], v[AGG_NU][JT], xp[AGG_NU], vm[AGG_NU], vd[AGG_NU];
+#pragma unroll
+            for (int u = 0; u < AGG_NU; ++u) {
+                // a dead slot holds its row's last entry (or a live row's first) with zero coefficients
+                const int src = g0 + e + u;
+                xg[u] = xp[u] = 0.f;
+#pragma unroll
+                for (int j = 0; j < JT; ++j) v[u][j] = 0.f;
+                vm[u] = vd[u] = 0.f;
+                if (gon) {
+                    const int col = __float_as_int(grp_bcast(mg.x, src));
+                    v[u][0] = grp_bcast(mg.y, src);
+                    if constexpr (JT > 1) v[u][1] = grp_bcast(mg.z, src);
+                    if constexpr (JT > 2) v[u][2] = grp_bcast(mg.w, src);
+#pragma unroll
+                    for (int j = 3; j < JT; ++j) v[u][j] = grp_bcast(f4_at(mx4, j - 3), src);
+                    xg[u] = a.xg[(long long)col * a.cg + ig];
+                }
+                if (pon) {
+                    const int col = __float_as_int(grp_bcast(mp.x, src));
+                    vm[u] = grp_bcast(mp.y, src);
+                    vd[u] = grp_bcast(mp.z, src);
+                    xp[u] = a.xp[(long long)col * a.cp + ip];
+                }
+            }
+            if (gon) {
+#pragma unroll
+                for (int u = 0; u < AGG_NU; ++u) {
+                    if (gbn) xg[u] = bn_z_s(xg[u], gmu, gsc, gb);
+#pragma unroll
+                    for (int j = 0; j < JT; ++j) acc[j] = fmaf(v[u][j], xg[u], acc[j]);
+                }
+            }
+            if (pon) {
+#pragma unroll
+                for (int u = 0; u < AGG_NU; ++u) {
+                    if (pbn) xp[u] = bn_z_s(xp[u], pmu, psc, pb);
+                    am = fmaf(vm[u], xp[u], am);
+                    ad = fmaf(vd[u], xp[u], ad);
+                }
+            }
+        }
+    }
+    if (r >= total) return;
+    float* o = a.out + (long long)r * a.ldo;
+    if constexpr (HG) {
+        if (i < a.cg) {
+#pragma unroll
+            for (int j = 0; j < JT; ++j) o[j * a.cg + i] = acc[j];
+        }
+    }
+    if constexpr (HP) {
+        const int base = JT * a.cg;
+        if (i < a.cp) {
+            o[base + i] = am;
+            o[base + a.cp + i] = ad;
+        }
+    }
+    // zero the row padding [K, ldo): the GEMMs run over the padded width
+    if (a.pad_from >= 0) {
+        const int kk = a.pad_from > 0 ? a.pad_from : JT * a.cg + (HP ? 2 * a.cp : 0);
+        for (int p = kk + i; p < a.ldo; p += AGG_NLPR) o[p] = 0.f;
+    }
+}
+
+template <int JT>
+static int agg_fwd_narrow(const AggFwdArgs& a0, bool hg, bool hp, hipStream_t s) {
+    AggFwdArgs a = a0;
+    const dim3 g(ceil_div(ceil_div(a.cap_rows, AGG_NGPW), AGG_WV));
+    a.stamps = clock_stamps((long long)g.x * AGG_WV);
+    if (hg && hp) HGNN_KLAUNCH((k_agg_fwd_narrow<JT, true, true>), g, dim3(AGG_NT), 0, s, a);
+    else if (hg) HGNN_KLAUNCH((k_agg_fwd_narrow<JT, true, false>), g, dim3(AGG_NT), 0, s, a);
+    else HGNN_KLAUNCH((k_agg_fwd_narrow<JT, false, true>), g, dim3(AGG_NT), 0, s, a);
+    HGNN_LAUNCH_CHECK();
+    return 0;
+}
+
 static int cpl_of(int c) {
     if (c <= 0) return 0;
     if (c <= 64) return 1;
@@ -517,6 +688,18 @@ int launch_agg_fwd(const AggFwdArgs& a, hipStream_t s) {
     if (a.cap_rows <= 0) return 0;
     if (a.j0 != 0 && (a.j0 != 2 || !a.xg || (a.diag && !a.err))) return HGNN_ERR_ARG;
     const dim3 g(ceil_div(a.cap_rows, AGG_WV));
+    // both parts at most AGG_NLPR channels wide (or absent): several rows per wave
+    const int cgn = a.xg && a.cg > 0 ? a.cg : 0, cpn = a.xp && a.cp > 0 ? a.cp : 0;
+    if (AGG_NARROW && a.j0 == 0 && cgn <= AGG_NLPR && cpn <= AGG_NLPR && (cgn > 0 || cpn > 0)) {
+        switch (a.jtot) {
+            case 3: return agg_fwd_narrow<3>(a, cgn > 0, cpn > 0, s);
+            case 4: return agg_fwd_narrow<4>(a, cgn > 0, cpn > 0, s);
+            case 5: return agg_fwd_narrow<5>(a, cgn > 0, cpn > 0, s);
+            case 6: return agg_fwd_narrow<6>(a, cgn > 0, cpn > 0, s);
+            case 7: return agg_fwd_narrow<7>(a, cgn > 0, cpn > 0, s);
+            default: return 2;
+        }
+    }
     switch (a.jtot) {
         case 3: return agg_fwd_cg<3>(a, g, s);
         case 4: return agg_fwd_cg<4>(a, g, s);
@@ -661,6 +844,90 @@ __global__ void __launch_bounds__(AGG_NT) k_agg_bwd(AggBwdArgs ga, AggBwdArgs pa
     }
 }
 
+// The backward gathers for c <= AGG_NLPR channels, AGG_NGPW rows per wave (see k_agg_fwd_narrow).  MODE 1: G, 2: P.
+// agg_bwd_g / agg_bwd_p run the fmaf chain over the row's entry slots padded per 64-entry chunk to their batch
+// (a dead slot: zero coefficients, so x = 0 in G and the last live row in P); here the wave runs to its longest
+// row, and a slot past the row's own padded count leaves the accumulator as it is, so the old value of an
+// accumulating launch meets the same operations.  A G slice with a zero coefficient is loaded (the slices of a
+// narrow row share its cache lines) and selected to 0: fmaf(0, 0, acc) as in agg_bwd_g_chunk.
+template <int JT, int MODE>
+__global__ void __launch_bounds__(AGG_NT) k_agg_bwd_narrow(AggBwdArgs a) {
+    WaveStamp stamp(a.stamps);
+    const int r0 = __builtin_amdgcn_readfirstlane((blockIdx.x * AGG_WV + (threadIdx.x >> 6)) * AGG_NGPW);
+    const int lane = threadIdx.x & 63, i = lane & (AGG_NLPR - 1), g0 = lane & ~(AGG_NLPR - 1);
+    const int total = *a.total_rows;
+    if (r0 >= total) return;
+    const int r = r0 + (lane >> 3);
+    const int rc = min(r, total - 1);  // (rows past the total: a live row, never stored)
+    const int ic = min(i, a.c - 1);
+    float acc = 0.f;
+    if (a.accumulate) acc = a.out[(long long)rc * a.ldo + ic];
+    NarrowList l;
+    l.init(row_info_lane(MODE == 1 ? a.g.rows : a.p.rows, rc));
+    // the slots agg_bwd_g / agg_bwd_p process of this row: whole 64-entry chunks, the last one padded to the batch
+    const int cnt = max(l.cnt, 0), rem = cnt & 63;
+    const int ub = MODE == 1 && rem > AGG_LONG ? AGG_LONG : 4;
+    const int proc = (cnt - rem) + (rem + ub - 1) / ub * ub;
+    const int stride = MODE == 1 ? a.g.stride : 4;
+    const float* entries = MODE == 1 ? a.g.entries : a.p.entries;
+    for (int e0 = 0; e0 < l.wmax; e0 += AGG_NLPR) {
+        bool live;
+        const float* q = entries + l.at(e0, i, live) * stride;
+        float4 me = *reinterpret_cast<const float4*>(q), mx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr (MODE == 1 && JT > 3) mx4 = *reinterpret_cast<const float4*>(q + 4);
+        if (!live) {
+            me.y = me.z = me.w = 0.f;
+            mx4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const int nn = min(AGG_NLPR, l.wmax - e0);
+        for (int e = 0; e < nn; e += AGG_NU) {
+            constexpr int NS = MODE == 1 ? JT : 2;
+            float x[AGG_NU][NS], v[AGG_NU][NS];
+#pragma unroll
+            for (int u = 0; u < AGG_NU; ++u) {
+                const int src = g0 + e + u;
+                const int col = __float_as_int(grp_bcast(me.x, src));
+                v[u][0] = grp_bcast(me.y, src);
+                v[u][1] = grp_bcast(me.z, src);
+                if constexpr (MODE == 1) {
+                    if constexpr (JT > 2) v[u][2] = grp_bcast(me.w, src);
+#pragma unroll
+                    for (int j = 3; j < JT; ++j) v[u][j] = grp_bcast(f4_at(mx4, j - 3), src);
+                    const float* s = a.ing + (long long)col * a.ldg + a.gofs + ic;
+#pragma unroll
+                    for (int j = 0; j < JT; ++j) x[u][j] = s[j * a.c];
+                } else {
+                    const float* s = a.inp + (long long)col * a.ldp + ic;
+                    x[u][0] = s[a.pofs_m];
+                    x[u][1] = s[a.pofs_d];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < AGG_NU; ++u) {
+                float t = acc;
+#pragma unroll
+                for (int j = 0; j < NS; ++j) {
+                    const float xv = MODE == 1 && v[u][j] == 0.f ? 0.f : x[u][j];
+                    t = fmaf(v[u][j], xv, t);
+                }
+                acc = e0 + e + u < proc ? t : acc;
+            }
+        }
+    }
+    if (r < total && i < a.c) a.out[(long long)r * a.ldo + i] = acc;
+}
+
+template <int JT>
+static int agg_bwd_narrow(const AggBwdArgs& a0, hipStream_t s) {
+    const dim3 g(ceil_div(ceil_div(a0.cap_rows, AGG_NGPW), AGG_WV));
+    AggBwdArgs a = a0;
+    a.stamps = clock_stamps((long long)g.x * AGG_WV);
+    if (a.ing) HGNN_KLAUNCH((k_agg_bwd_narrow<JT, 1>), g, dim3(AGG_NT), 0, s, a);
+    else HGNN_KLAUNCH((k_agg_bwd_narrow<3, 2>), g, dim3(AGG_NT), 0, s, a);
+    HGNN_LAUNCH_CHECK();
+    return 0;
+}
+
 static bool bwd_vec_g(int cpl, const AggBwdArgs& a) {
     return vec_ok(cpl, a.c, a.ing, {a.ldg, a.gofs}) && vec_ok(cpl, a.c, a.out, {a.ldo});
 }
@@ -686,6 +953,7 @@ static int agg_bwd_single(const AggBwdArgs& a0, hipStream_t s) {
 
 template <int JT>
 static int agg_bwd_c(const AggBwdArgs& a, hipStream_t s) {
+    if (AGG_NARROW && a.c > 0 && a.c <= AGG_NLPR) return agg_bwd_narrow<JT>(a, s);
     switch (cpl_of(a.c)) {
         case 1: return agg_bwd_single<JT, 1>(a, s);
         case 2: return agg_bwd_single<JT, 2>(a, s);

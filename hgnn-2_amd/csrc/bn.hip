@@ -246,6 +246,18 @@ __global__ void __launch_bounds__(256) k_bn_bwd_part4(BnBwdArgs a) {
     float4 s[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    // the thread's first eight rows (all of them up to c = 128) go out before mean / std are read: one round trip
+    // instead of mean / std and then a round per four rows (a 64-row tile per block leaves about a block per CU, so
+    // the launch is as long as one block's chain of round trips); clamped into the tile, a row past it is dropped below
+    constexpr int U0 = 8;
+    float4 dz0[U0], yv0[U0];
+#pragma unroll
+    for (int u = 0; u < U0; ++u) {
+        if (u * RG >= 64) break;  // (uniform: fewer than eight rows per thread, c < 128)
+        const long long i = (long long)min(r0 + rg + u * RG, r1 - 1) * a.c + 4 * lane;
+        dz0[u] = ld4(a.dz + i);
+        yv0[u] = ld4(a.y + i);
+    }
     if (rg < RG) {
         float mu[4], isd[4];
 #pragma unroll
@@ -266,6 +278,10 @@ __global__ void __launch_bounds__(256) k_bn_bwd_part4(BnBwdArgs a) {
             }
         };
         int r = r0 + rg;
+#pragma unroll
+        for (int u = 0; u < U0; ++u)
+            if (r + u * RG < r1) acc(dz0[u], yv0[u]);
+        r += U0 * RG;
         for (; r + 3 * RG < r1; r += 4 * RG) {
             float4 dz[4], yv[4];
 #pragma unroll
@@ -320,6 +336,32 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply4(BnBwdArgs a) {
     const int total = *a.total_rows;
     const float wv = *a.w;
     const float inv_n = total > 0 ? 1.0f / (float)total : 0.f;
+    const int r0 = blockIdx.x * 64;
+    const bool tile = r0 < total;  // (block 0 of an empty batch: only dw / db and the zeroing)
+    const int r1 = min(total, r0 + 64);
+    const int L = a.c >> 2, RG = min(256 / L, 64);  // see k_bn_bwd_part4
+    const int lane = threadIdx.x % L, rg = threadIdx.x / L;
+    // One round trip: the thread's first eight rows of dz / y and its channels' mean / std go out before the
+    // accumulator copies are read, so the tile's loads are in flight while the statistics come in (the copies first,
+    // then a barrier, then the tile's loads were two dependent round trips per block).  Row addresses are clamped
+    // into the tile, so the loads are unconditional; a row past the tile is dropped below.
+    constexpr int U0 = 8;
+    float4 dz0[U0], yv0[U0];
+    float mu[4], sd[4];
+    if (tile) {
+#pragma unroll
+        for (int u = 0; u < U0; ++u) {
+            if (u * RG >= 64) break;  // (uniform: fewer than eight rows per thread, c < 128)
+            const long long i = (long long)min(r0 + rg + u * RG, r1 - 1) * a.c + 4 * lane;
+            dz0[u] = ld4(a.dz + i);
+            yv0[u] = ld4(a.y + i);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            mu[i] = a.mean[4 * lane + i];
+            sd[i] = a.std[4 * lane + i];
+        }
+    }
     // atomic path: the statistics m1 / m2 of every channel from the accumulator copies, once per block into LDS
     __shared__ float sm12[2][1024];
     if (a.acc64) {
@@ -334,35 +376,15 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply4(BnBwdArgs a) {
                 a.acc64_zero[i] = 0.0;
         __syncthreads();
     }
-    if (blockIdx.x == 0) {
-        __shared__ double redd[4];
-        double t1 = 0.0, t2 = 0.0;
-        for (int ch = threadIdx.x; ch < a.c; ch += blockDim.x) {
-            t1 += (double)(a.acc64 ? bn_acc_stat(a.acc64, a.c, 2, ch) : a.sums[ch * 4 + 2]);
-            t2 += (double)(a.acc64 ? bn_acc_stat(a.acc64, a.c, 3, ch) : a.sums[ch * 4 + 3]);
-        }
-        const double T1 = block_sum_d(t1, redd);
-        const double T2 = block_sum_d(t2, redd);
-        if (threadIdx.x == 0) {
-            *a.dw = (float)T1;
-            *a.db = (float)T2;
-        }
-    }
-    const int r0 = blockIdx.x * 64;
-    if (r0 >= total) return;
-    const int r1 = min(total, r0 + 64);
-    const int L = a.c >> 2, RG = min(256 / L, 64);  // see k_bn_bwd_part4
-    const int lane = threadIdx.x % L, rg = threadIdx.x / L;
     __shared__ float4 red[256];
     float4 cs = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (rg < RG) {
-        float mu[4], isd[4], m1[4], m2[4];
+    if (tile && rg < RG) {
+        float isd[4], m1[4], m2[4];
         bool relu[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int ch = 4 * lane + i;
-            mu[i] = a.mean[ch];
-            isd[i] = 1.0f / a.std[ch];
+            isd[i] = 1.0f / sd[i];
             m1[i] = (a.acc64 ? sm12[0][ch] : a.sums[ch * 4 + 0]) * inv_n;
             m2[i] = (a.acc64 ? sm12[1][ch] : a.sums[ch * 4 + 1]) * inv_n;
             relu[i] = ch >= a.relu_from;
@@ -378,6 +400,11 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply4(BnBwdArgs a) {
             *reinterpret_cast<float4*>(a.dy + i) = d;
         };
         int r = r0 + rg;
+#pragma unroll
+        for (int u = 0; u < U0; ++u)
+            if (r + u * RG < r1) one((long long)(r + u * RG) * a.c + 4 * lane, yv0[u], dz0[u]);
+        r += U0 * RG;
+        // (more than eight rows per thread: c > 128)
         for (; r + 7 * RG < r1; r += 8 * RG) {
             float4 dz[8], yv[8];
 #pragma unroll
@@ -405,7 +432,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply4(BnBwdArgs a) {
             one(i, ld4(a.y + i), ld4(a.dz + i));
         }
     }
-    if (a.dbpart) {
+    if (tile && a.dbpart) {
         red[threadIdx.x] = cs;
         __syncthreads();
         for (int ch = threadIdx.x; ch < a.c; ch += 256) {
@@ -413,6 +440,22 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply4(BnBwdArgs a) {
             float t = 0.f;
             for (int q = 0; q < RG; ++q) t += f4c(red[q * L + l], comp);
             a.dbpart[(long long)blockIdx.x * a.c + ch] = t;
+        }
+    }
+    // the BN scalar gradients, by block 0 behind its own tile's stores (in front of them they held its tile back by a
+    // round trip and two block-wide fp64 reductions)
+    if (blockIdx.x == 0) {
+        __shared__ double redd[4];
+        double t1 = 0.0, t2 = 0.0;
+        for (int ch = threadIdx.x; ch < a.c; ch += blockDim.x) {
+            t1 += (double)(a.acc64 ? bn_acc_stat(a.acc64, a.c, 2, ch) : a.sums[ch * 4 + 2]);
+            t2 += (double)(a.acc64 ? bn_acc_stat(a.acc64, a.c, 3, ch) : a.sums[ch * 4 + 3]);
+        }
+        const double T1 = block_sum_d(t1, redd);
+        const double T2 = block_sum_d(t2, redd);
+        if (threadIdx.x == 0) {
+            *a.dw = (float)T1;
+            *a.db = (float)T2;
         }
     }
 }
