@@ -13,9 +13,12 @@
 // everything else is integer counting.  A dense accumulation over a row's pattern visits exactly the terms
 // the host's sparse rows hold, in the same order.
 //
-// Bounds: n <= 32, m <= 72 (k_extract_reg's QM9 bounds), J + 2 <= 5.  LDS per workgroup at J + 2 = 3 / 4 / 5:
-// see DESIGN.md §4 (the m x m fp32 tiles of base^2 and base^4 are the bulk; the base slice is not stored:
-// A is 32 x 32, and AL[a][b] is w(b) under a condition on the edge table).
+// Bounds: J + 2 <= 5, and per graph what one workgroup holds in LDS (BtCaps): with the line graph (dual) n <= 32,
+// m <= 72 (k_extract_reg's QM9 bounds); the node family alone (dual == 0) n <= 64, where a row's pattern is two
+// 32-bit words.  Both are instantiations of the one kernel.  A dual == 0 batch whose largest graph has at most
+// 32 nodes is built by the narrow instantiation.  LDS per workgroup at J + 2 = 3 / 4 / 5: see DESIGN.md §4 (the
+// m x m fp32 tiles of base^2 and base^4 are the bulk; the base slice is not stored: A is its own tile, and
+// AL[a][b] is w(b) under a condition on the edge table).
 #include <string.h>
 
 #include "common.h"
@@ -28,46 +31,64 @@ void csr_layout_offsets(hgnn_csr_layout& L);
 namespace {
 
 constexpr int BT_THREADS = 256;
-constexpr int BT_NCAP = 32;  // nodes
-constexpr int BT_MCAP = 72;  // edge slots
-constexpr int BT_MW = 3;     // 32-bit words of a row's column bitmap
 constexpr int BT_HDR = 4;    // scratch: header words {ok, 0, 0, 0}
 constexpr int BT_TAB = 12;   // scratch words per batch graph: {graph, skip, node0, edge0, entry start[6], 0, 0}
 enum { K_W = 0, K_WT = 1, K_WL = 2, K_WLT = 3, K_PN = 4, K_PE = 5, K_N = 6 };
 
-template <int JT>
+// What one workgroup can hold.  NCAP: nodes, and the stride of the A tile; MCAP: rows of the widest family (edge
+// slots with the line graph, nodes without), and the stride of the base^2 / base^4 tiles; MW: 32-bit words of a
+// row's column bitmap; LINE: the line-graph family (edge table, WL, Pm / Pd) is built when the launch is dual.
+template <int NCAP_, int MCAP_, bool LINE_>
+struct BtCaps {
+    static constexpr int NCAP = NCAP_, MCAP = MCAP_, MW = (MCAP_ + 31) / 32;
+    static constexpr bool LINE = LINE_;
+    static constexpr int LN = LINE_ ? NCAP_ : 1, LM = LINE_ ? MCAP_ : 1;  // extents of what only LINE uses
+};
+using BtNarrow = BtCaps<32, 72, true>;  // both families (k_extract_reg's QM9 bounds); the builder of every dual launch
+using BtWide = BtCaps<64, 64, false>;   // the node family alone: a row's pattern is 64 bits
+
+template <int JT, class C>
 struct BtLds {
-    float A[BT_NCAP * BT_NCAP];
-    uint32_t mb[BT_MCAP][BT_MW], m2[BT_MCAP][BT_MW], m4[BT_MCAP][BT_MW];  // patterns of base, base^2, base^4
-    uint32_t U[BT_MCAP][BT_MW], UT[BT_MCAP][BT_MW];                        // the union pattern and its transpose
-    int rstart[BT_MCAP], tstart[BT_MCAP];
-    float deg[BT_MCAP];
-    int esrc[BT_MCAP], etgt[BT_MCAP];
-    float ew[BT_MCAP];
-    uint32_t pn[BT_NCAP][BT_MW], pe[BT_MCAP];  // incidence patterns: node -> slots, slot -> nodes
-    int pnstart[BT_NCAP], pestart[BT_MCAP];
-    uint32_t rowmask[BT_NCAP];
-    int rowpre[BT_NCAP];
+    float A[C::NCAP * C::NCAP];
+    uint32_t mb[C::MCAP][C::MW], m2[C::MCAP][C::MW], m4[C::MCAP][C::MW];  // patterns of base, base^2, base^4
+    uint32_t U[C::MCAP][C::MW], UT[C::MCAP][C::MW];                        // the union pattern and its transpose
+    int rstart[C::MCAP], tstart[C::MCAP];
+    float deg[C::MCAP];
+    int esrc[C::LM], etgt[C::LM];
+    float ew[C::LM];
+    uint32_t pn[C::LN][C::MW], pe[C::LM];  // incidence patterns: node -> slots, slot -> nodes
+    int pnstart[C::LN], pestart[C::LM];
+    uint32_t rowmask[C::LN];
+    int rowpre[C::LN];
     int m, B, bad, nnz, nnzp;
-    unsigned char inc[BT_NCAP][BT_MCAP];  // 0: none, 1: Pm = 1, Pd = 1, 2: Pm = 1, Pd = -1
+    unsigned char inc[C::LN][C::LM];  // 0: none, 1: Pm = 1, Pd = 1, 2: Pm = 1, Pd = -1
     // (not zeroed: written over [0, dim) x [0, dim) before they are read)
-    float p2[JT >= 4 ? BT_MCAP * BT_MCAP : 1];
-    float p4[JT >= 5 ? BT_MCAP * BT_MCAP : 1];
+    float p2[JT >= 4 ? C::MCAP * C::MCAP : 1];
+    float p4[JT >= 5 ? C::MCAP * C::MCAP : 1];
 };
 
-__device__ __forceinline__ int bits3(const uint32_t* row) { return __popc(row[0]) + __popc(row[1]) + __popc(row[2]); }
-// set bits of the row below column c
-__device__ __forceinline__ int rank3(const uint32_t* row, int c) {
-    int p = __popc(row[c >> 5] & ((1u << (c & 31)) - 1u));
-    if (c >= 32) p += __popc(row[0]);
-    if (c >= 64) p += __popc(row[1]);
+template <int MW>
+__device__ __forceinline__ int bt_bits(const uint32_t* row) {
+    int p = __popc(row[0]);
+#pragma unroll
+    for (int w = 1; w < MW; ++w) p += __popc(row[w]);
     return p;
 }
-__device__ __forceinline__ bool has3(const uint32_t* row, int c) { return (row[c >> 5] >> (c & 31)) & 1u; }
+// set bits of the row below column c
+template <int MW>
+__device__ __forceinline__ int bt_rank(const uint32_t* row, int c) {
+    int p = __popc(row[c >> 5] & ((1u << (c & 31)) - 1u));
+#pragma unroll
+    for (int w = 1; w < MW; ++w)
+        if (c >= 32 * w) p += __popc(row[w - 1]);
+    return p;
+}
+__device__ __forceinline__ bool bt_has(const uint32_t* row, int c) { return (row[c >> 5] >> (c & 31)) & 1u; }
 
+template <int LD>
 struct BaseA {  // the node graph: A itself
     const float* A;
-    __device__ __forceinline__ float val(int r, int c) const { return A[r * BT_NCAP + c]; }
+    __device__ __forceinline__ float val(int r, int c) const { return A[r * LD + c]; }
 };
 struct BaseL {  // the line graph: AL[a][b] = w(b) iff tgt(a) == src(b) and src(a) != tgt(b) (builder.cpp line_graph)
     const int *src, *tgt;
@@ -97,21 +118,21 @@ struct BtArgs {
 
 // dst = src^2 over the pattern `mask` of src, as builder.cpp square(): per (i, j) the products a(i,k) * b(k,j) of
 // the entries both rows hold, k ascending, in fp64; an entry where the sum is not 0.0, its value rounded to fp32.
-template <class Src>
-__device__ __forceinline__ void bt_square(int dim, Src src, const uint32_t (*mask)[BT_MW], float* dst,
-                                          uint32_t (*dmask)[BT_MW]) {
+template <class C, class Src>
+__device__ __forceinline__ void bt_square(int dim, Src src, const uint32_t (*mask)[C::MW], float* dst,
+                                          uint32_t (*dmask)[C::MW]) {
     for (int idx = threadIdx.x; idx < dim * dim; idx += BT_THREADS) {
         const int i = idx / dim, j = idx - i * dim;
         double acc = 0.0;
-        for (int w = 0; w < BT_MW; ++w) {
+        for (int w = 0; w < C::MW; ++w) {
             uint32_t bits = mask[i][w];
             while (bits) {
                 const int k = 32 * w + __ffs(bits) - 1;
                 bits &= bits - 1u;
-                if (has3(mask[k], j)) acc = __dadd_rn(acc, __dmul_rn((double)src(i, k), (double)src(k, j)));
+                if (bt_has(mask[k], j)) acc = __dadd_rn(acc, __dmul_rn((double)src(i, k), (double)src(k, j)));
             }
         }
-        dst[i * BT_MCAP + j] = (float)acc;
+        dst[i * C::MCAP + j] = (float)acc;
         if (acc != 0.0) atomicOr(&dmask[i][j >> 5], 1u << (j & 31));
     }
 }
@@ -119,12 +140,12 @@ __device__ __forceinline__ void bt_square(int dim, Src src, const uint32_t (*mas
 // One operator family (builder.cpp slices() + transpose()) of a dim x dim base: the slices I, diag(row sum), base,
 // base^2, base^4 as one row list over the union pattern, and its transpose.  Returns the entry count; writes the
 // lists only if it is the count the records promised.  Every thread of the workgroup calls it.
-template <int JT, bool COUNT, class Base>
-__device__ int bt_family(BtLds<JT>& s, int dim, Base base, const BtOut& o, int col0) {
+template <int JT, bool COUNT, class C, class Base>
+__device__ int bt_family(BtLds<JT, C>& s, int dim, Base base, const BtOut& o, int col0) {
     constexpr int SW = JT <= 3 ? 4 : 8;
     const int tid = threadIdx.x;
-    for (int t = tid; t < BT_MCAP * BT_MW; t += BT_THREADS) {
-        const int r = t / BT_MW, w = t - r * BT_MW;
+    for (int t = tid; t < C::MCAP * C::MW; t += BT_THREADS) {
+        const int r = t / C::MW, w = t - r * C::MW;
         uint32_t bits = 0u;
         if (r < dim)
             for (int c = 32 * w; c < min(32 * w + 32, dim); ++c) bits |= (uint32_t)(base.val(r, c) != 0.f) << (c & 31);
@@ -135,7 +156,7 @@ __device__ int bt_family(BtLds<JT>& s, int dim, Base base, const BtOut& o, int c
     __syncthreads();
     if (tid < dim) {
         double d = 0.0;
-        for (int w = 0; w < BT_MW; ++w) {
+        for (int w = 0; w < C::MW; ++w) {
             uint32_t bits = s.mb[tid][w];
             while (bits) {
                 const int c = 32 * w + __ffs(bits) - 1;
@@ -146,36 +167,36 @@ __device__ int bt_family(BtLds<JT>& s, int dim, Base base, const BtOut& o, int c
         s.deg[tid] = (float)d;
     }
     if constexpr (JT >= 4) {
-        bt_square(dim, [&](int r, int c) { return base.val(r, c); }, s.mb, s.p2, s.m2);
+        bt_square<C>(dim, [&](int r, int c) { return base.val(r, c); }, s.mb, s.p2, s.m2);
         __syncthreads();
     }
     if constexpr (JT >= 5) {
-        bt_square(dim, [&](int r, int c) { return s.p2[r * BT_MCAP + c]; }, s.m2, s.p4, s.m4);
+        bt_square<C>(dim, [&](int r, int c) { return s.p2[r * C::MCAP + c]; }, s.m2, s.p4, s.m4);
         __syncthreads();
     }
-    for (int t = tid; t < dim * BT_MW; t += BT_THREADS) {
-        const int r = t / BT_MW, w = t - r * BT_MW;
+    for (int t = tid; t < dim * C::MW; t += BT_THREADS) {
+        const int r = t / C::MW, w = t - r * C::MW;
         uint32_t u = s.mb[r][w] | s.m2[r][w] | s.m4[r][w];
         if ((r >> 5) == w) u |= 1u << (r & 31);  // the diagonal is always present (slice I)
         s.U[r][w] = u;
     }
     __syncthreads();
-    for (int t = tid; t < dim * BT_MW; t += BT_THREADS) {
-        const int c = t / BT_MW, w = t - c * BT_MW;
+    for (int t = tid; t < dim * C::MW; t += BT_THREADS) {
+        const int c = t / C::MW, w = t - c * C::MW;
         uint32_t bits = 0u;
-        for (int r = 32 * w; r < min(32 * w + 32, dim); ++r) bits |= (uint32_t)has3(s.U[r], c) << (r & 31);
+        for (int r = 32 * w; r < min(32 * w + 32, dim); ++r) bits |= (uint32_t)bt_has(s.U[r], c) << (r & 31);
         s.UT[c][w] = bits;
     }
     __syncthreads();
     if (tid < dim) {
         int rs = 0, ts = 0;
         for (int q = 0; q < tid; ++q) {
-            rs += bits3(s.U[q]);
-            ts += bits3(s.UT[q]);
+            rs += bt_bits<C::MW>(s.U[q]);
+            ts += bt_bits<C::MW>(s.UT[q]);
         }
         s.rstart[tid] = rs;
         s.tstart[tid] = ts;
-        if (tid == dim - 1) s.nnz = rs + bits3(s.U[tid]);
+        if (tid == dim - 1) s.nnz = rs + bt_bits<C::MW>(s.U[tid]);
     }
     if (dim == 0 && tid == 0) s.nnz = 0;
     __syncthreads();
@@ -183,21 +204,21 @@ __device__ int bt_family(BtLds<JT>& s, int dim, Base base, const BtOut& o, int c
     if constexpr (!COUNT) {
         if (nnz == o.expect && nnz == o.expectT) {
             if (tid < dim) {
-                o.rows[o.row0 + tid] = RowInfo{o.ent0 + s.rstart[tid], bits3(s.U[tid])};
-                o.rowsT[o.row0 + tid] = RowInfo{o.entT0 + s.tstart[tid], bits3(s.UT[tid])};
+                o.rows[o.row0 + tid] = RowInfo{o.ent0 + s.rstart[tid], bt_bits<C::MW>(s.U[tid])};
+                o.rowsT[o.row0 + tid] = RowInfo{o.entT0 + s.tstart[tid], bt_bits<C::MW>(s.UT[tid])};
                 if (o.deg) o.deg[tid] = s.deg[tid];
             }
             for (int idx = tid; idx < dim * dim; idx += BT_THREADS) {
                 const int r = idx / dim, c = idx - r * dim;
-                if (!has3(s.U[r], c)) continue;
+                if (!bt_has(s.U[r], c)) continue;
                 const bool dg = r == c;
                 const float v0 = dg ? 1.f : 0.f, v1 = dg ? s.deg[r] : 0.f, v2 = base.val(r, c);
-                float* e = o.ent + (size_t)(o.ent0 + s.rstart[r] + rank3(s.U[r], c)) * SW;
-                float* et = o.entT + (size_t)(o.entT0 + s.tstart[c] + rank3(s.UT[c], r)) * SW;
+                float* e = o.ent + (size_t)(o.ent0 + s.rstart[r] + bt_rank<C::MW>(s.U[r], c)) * SW;
+                float* et = o.entT + (size_t)(o.entT0 + s.tstart[c] + bt_rank<C::MW>(s.UT[c], r)) * SW;
                 *reinterpret_cast<float4*>(e) = make_float4(__int_as_float(col0 + c), v0, v1, v2);
                 *reinterpret_cast<float4*>(et) = make_float4(__int_as_float(col0 + r), v0, v1, v2);
                 if constexpr (SW == 8) {
-                    const float v3 = s.p2[r * BT_MCAP + c], v4 = JT >= 5 ? s.p4[r * BT_MCAP + c] : 0.f;
+                    const float v3 = s.p2[r * C::MCAP + c], v4 = JT >= 5 ? s.p4[r * C::MCAP + c] : 0.f;
                     *reinterpret_cast<float4*>(e + 4) = make_float4(v3, v4, 0.f, 0.f);
                     *reinterpret_cast<float4*>(et + 4) = make_float4(v3, v4, 0.f, 0.f);
                 }
@@ -220,9 +241,10 @@ __device__ __forceinline__ void bt_record(int32_t* out, long long g, int n, int 
     r[9] = 0;
 }
 
-template <int JT, bool COUNT>
+template <int JT, bool COUNT, class C>
 __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
-    __shared__ BtLds<JT> s;
+    using Lds = BtLds<JT, C>;
+    __shared__ Lds s;
     const int tid = threadIdx.x;
     long long g;
     const int32_t *tab = nullptr, *rec = nullptr;
@@ -241,7 +263,7 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
     const long long nn0 = a.v.d_node_off[g], n64 = a.v.d_node_off[g + 1] - nn0;
     const long long a0 = a.v.d_adj_off[g], c64 = a.v.d_adj_off[g + 1] - a0;
     int flags = 0;
-    if (n64 < 1 || n64 > BT_NCAP) flags = HGNN_PACK_FLAG_BOUNDS;
+    if (n64 < 1 || n64 > C::NCAP) flags = HGNN_PACK_FLAG_BOUNDS;
     else if (c64 < 0 || c64 > n64 * n64) flags = HGNN_PACK_FLAG_COO;  // strictly ascending entries are at most n^2
     if (flags) {
         if constexpr (COUNT) bt_record(a.counts_out, g, (int)max(min(n64, 0x7fffffffll), 0ll), 0, 0, 0, 0, flags);
@@ -250,7 +272,7 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
     const int n = (int)n64, cnt = (int)c64;
     {
         uint32_t* z = reinterpret_cast<uint32_t*>(&s);
-        for (int i = tid; i < (int)(offsetof(BtLds<JT>, p2) / 4); i += BT_THREADS) z[i] = 0u;
+        for (int i = tid; i < (int)(offsetof(Lds, p2) / 4); i += BT_THREADS) z[i] = 0u;
     }
     __syncthreads();
     for (int e = tid; e < cnt; e += BT_THREADS) {
@@ -260,7 +282,7 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
             const int pi = a.v.d_adj_ij[2 * (a0 + e) - 2], pj = a.v.d_adj_ij[2 * (a0 + e) - 1];
             ok = ok && (pi < i || (pi == i && pj < j));
         }
-        if (ok) s.A[i * BT_NCAP + j] = a.v.d_adj_w[a0 + e];
+        if (ok) s.A[i * C::NCAP + j] = a.v.d_adj_w[a0 + e];
         else s.bad = 1;
     }
     __syncthreads();
@@ -268,30 +290,35 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
         if constexpr (COUNT) bt_record(a.counts_out, g, n, 0, 0, 0, 0, HGNN_PACK_FLAG_COO);
         return;
     }
-    if (tid < n) {
-        uint32_t bits = 0u;
-        for (int c = 0; c < n; ++c) bits |= (uint32_t)(s.A[tid * BT_NCAP + c] != 0.f) << c;
-        s.rowmask[tid] = bits;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        // m = nnz(A) with the diagonal (Q2); B = the bonds, the upper-triangle nonzeros, ranked row-major
-        int m = 0, B = 0;
-        for (int r = 0; r < n; ++r) {
-            m += __popc(s.rowmask[r]);
-            s.rowpre[r] = B;
-            B += __popc(s.rowmask[r] & ~((2u << r) - 1u));
+    int m = 0, B = 0;  // without the line graph there are no edge slots
+    if constexpr (C::LINE) {
+        static_assert(C::NCAP == 32, "the edge table holds a row of A in one 32-bit word");
+        if (tid < n) {
+            uint32_t bits = 0u;
+            for (int c = 0; c < n; ++c) bits |= (uint32_t)(s.A[tid * C::NCAP + c] != 0.f) << c;
+            s.rowmask[tid] = bits;
         }
-        s.m = a.dual ? m : 0;
-        s.B = B;
-    }
-    __syncthreads();
-    const int m = s.m, B = s.B;
-    if (a.dual && m > BT_MCAP) flags = HGNN_PACK_FLAG_BOUNDS;
-    else if (a.dual && B > 0 && B >= m) flags = HGNN_PACK_FLAG_INDEX;  // edge_slots(): bond B - 1 writes column B
-    if (flags) {
-        if constexpr (COUNT) bt_record(a.counts_out, g, n, m, 0, 0, 0, flags);
-        return;
+        __syncthreads();
+        if (tid == 0) {
+            // m = nnz(A) with the diagonal (Q2); B = the bonds, the upper-triangle nonzeros, ranked row-major
+            int m = 0, B = 0;
+            for (int r = 0; r < n; ++r) {
+                m += __popc(s.rowmask[r]);
+                s.rowpre[r] = B;
+                B += __popc(s.rowmask[r] & ~((2u << r) - 1u));
+            }
+            s.m = a.dual ? m : 0;
+            s.B = B;
+        }
+        __syncthreads();
+        m = s.m;
+        B = s.B;
+        if (a.dual && m > C::MCAP) flags = HGNN_PACK_FLAG_BOUNDS;
+        else if (a.dual && B > 0 && B >= m) flags = HGNN_PACK_FLAG_INDEX;  // edge_slots(): bond B - 1 writes column B
+        if (flags) {
+            if constexpr (COUNT) bt_record(a.counts_out, g, n, m, 0, 0, 0, flags);
+            return;
+        }
     }
     BtOut ow{}, ol{};
     if constexpr (!COUNT) {
@@ -303,17 +330,18 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
         ol = BtOut{a.rows[K_WL], a.rows[K_WLT], a.ent[K_WL], a.ent[K_WLT], a.xl + edge0, edge0, tab[4 + K_WL],
                    tab[4 + K_WLT], rec[2 + K_WL], rec[2 + K_WLT]};
     }
-    const int nnz_w = bt_family<JT, COUNT>(s, n, BaseA{s.A}, ow, node0);
+    const int nnz_w = bt_family<JT, COUNT>(s, n, BaseA<C::NCAP>{s.A}, ow, node0);
     int nnz_l = 0, nnz_p = 0;
-    if (a.dual) {
+    // (without C::LINE this block is never entered and the compiler drops it: the arrays it names have extent 1)
+    if (C::LINE && a.dual) {
         // the edge table with the reference's quirk Q1: slot k < B is forward(bond k), slot B is reverse(bond B - 1),
         // later slots stay (0, 0, 0)
-        for (int idx = tid; idx < n * BT_NCAP; idx += BT_THREADS) {
+        for (int idx = tid; idx < n * C::NCAP; idx += BT_THREADS) {
             const int i = idx >> 5, j = idx & 31;
             const uint32_t up = s.rowmask[i] & ~((2u << i) - 1u);
             if (j > i && ((up >> j) & 1u)) {
                 const int k = s.rowpre[i] + __popc(up & ((1u << j) - 1u));
-                const float w = s.A[i * BT_NCAP + j];
+                const float w = s.A[i * C::NCAP + j];
                 s.esrc[k] = i;
                 s.etgt[k] = j;
                 s.ew[k] = w;
@@ -352,7 +380,7 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
         if (tid < max(n, m)) {
             int ps = 0, es = 0;
             for (int q = 0; q < tid; ++q) {
-                if (q < n) ps += bits3(s.pn[q]);
+                if (q < n) ps += bt_bits<C::MW>(s.pn[q]);
                 if (q < m) es += __popc(s.pe[q]);
             }
             if (tid < n) s.pnstart[tid] = ps;
@@ -365,14 +393,14 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_graph(BtArgs a) {
         if constexpr (!COUNT) {
             if (nnz_p == rec[2 + K_PN] && nnz_p == rec[2 + K_PE]) {
                 const int pn0 = tab[4 + K_PN], pe0 = tab[4 + K_PE];
-                if (tid < n) a.rows[K_PN][node0 + tid] = RowInfo{pn0 + s.pnstart[tid], bits3(s.pn[tid])};
+                if (tid < n) a.rows[K_PN][node0 + tid] = RowInfo{pn0 + s.pnstart[tid], bt_bits<C::MW>(s.pn[tid])};
                 if (tid < m) a.rows[K_PE][edge0 + tid] = RowInfo{pe0 + s.pestart[tid], (int)__popc(s.pe[tid])};
                 for (int idx = tid; idx < n * m; idx += BT_THREADS) {
                     const int i = idx / m, k = idx - i * m;
                     const int c = s.inc[i][k];
                     if (!c) continue;
                     const float pd = c == 1 ? 1.f : -1.f;
-                    float* e = a.ent[K_PN] + (size_t)(pn0 + s.pnstart[i] + rank3(s.pn[i], k)) * 4;
+                    float* e = a.ent[K_PN] + (size_t)(pn0 + s.pnstart[i] + bt_rank<C::MW>(s.pn[i], k)) * 4;
                     float* et = a.ent[K_PE] + (size_t)(pe0 + s.pestart[k] + __popc(s.pe[k] & ((1u << i) - 1u))) * 4;
                     *reinterpret_cast<float4*>(e) = make_float4(__int_as_float(edge0 + k), 1.f, pd, 0.f);
                     *reinterpret_cast<float4*>(et) = make_float4(__int_as_float(node0 + i), 1.f, pd, 0.f);
@@ -470,13 +498,13 @@ __global__ void __launch_bounds__(BT_THREADS) k_batch_offsets(BtOffArgs a) {
     }
 }
 
-template <bool COUNT>
+template <bool COUNT, class C>
 int bt_launch(const BtArgs& a, int jt, long long blocks, hipStream_t s) {
     const dim3 grid((unsigned)blocks), block(BT_THREADS);
     switch (jt) {
-        case 3: HGNN_KLAUNCH(k_batch_graph<3, COUNT>, grid, block, 0, s, a); break;
-        case 4: HGNN_KLAUNCH(k_batch_graph<4, COUNT>, grid, block, 0, s, a); break;
-        case 5: HGNN_KLAUNCH(k_batch_graph<5, COUNT>, grid, block, 0, s, a); break;
+        case 3: HGNN_KLAUNCH(k_batch_graph<3, COUNT, C>, grid, block, 0, s, a); break;
+        case 4: HGNN_KLAUNCH(k_batch_graph<4, COUNT, C>, grid, block, 0, s, a); break;
+        case 5: HGNN_KLAUNCH(k_batch_graph<5, COUNT, C>, grid, block, 0, s, a); break;
         default: return HGNN_ERR_UNSUPPORTED;
     }
     HGNN_LAUNCH_CHECK();
@@ -502,7 +530,10 @@ int hgnn_pack_count(const hgnn_pack_view* view, int J, int dual, int32_t* d_coun
     a.v = *view;
     a.counts_out = d_counts;
     a.dual = dual ? 1 : 0;
-    return bt_launch<true>(a, J + 2, view->graphs, static_cast<hipStream_t>(stream));
+    // without the line graph the records are the wide builder's, whichever builder a batch then takes
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return a.dual ? bt_launch<true, BtNarrow>(a, J + 2, view->graphs, s)
+                  : bt_launch<true, BtWide>(a, J + 2, view->graphs, s);
 }
 
 size_t hgnn_csr_batch_build_device_scratch_bytes(int bs) {
@@ -558,7 +589,10 @@ int hgnn_csr_batch_build_device(const hgnn_pack_view* view, const int32_t* d_cou
         a.rows[k] = reinterpret_cast<RowInfo*>(img + L.off_rows[k]);
         a.ent[k] = reinterpret_cast<float*>(img + L.off_entries[k]);
     }
-    return bt_launch<false>(a, jt, bs, s);
+    // a node-family batch whose largest graph fits the narrow builder takes it; a graph past the chosen builder's
+    // node cap (a layout that is not of these records) is left as zeros
+    if (!a.dual && L.nmax > BtNarrow::NCAP) return bt_launch<false, BtWide>(a, jt, bs, s);
+    return bt_launch<false, BtNarrow>(a, jt, bs, s);
 }
 
 }  // extern "C"

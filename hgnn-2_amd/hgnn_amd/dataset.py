@@ -233,8 +233,11 @@ class DevicePack:
     enqueues hgnn_csr_batch_build_device on the current stream -- the image hgnn_csr_batch_build writes on the
     host, byte for byte, with no host work per graph and no synchronisation.
 
-    The device builder takes graphs of at most 32 nodes and 72 edge slots and J <= 3; a batch with a larger
-    graph, and every batch at J > 3, is built by the host batcher (pack.batches).  A batch with a graph whose
+    The device builder takes J <= 3 and, with dual=True, graphs of at most 32 nodes and 72 edge slots; with
+    dual=False (the node-graph family alone: GNN_simple) graphs of at most 64 nodes with any number of bonds, so
+    SBM-50 and the generated data set (datagen.three_collinear_points, 3 to 49 nodes) are built on the device.
+    A batch with a larger graph, and every batch at J > 3, is built by the host batcher (pack.batches): the
+    records' HGNN_PACK_FLAG_BOUNDS decides, per batch.  A batch with a graph whose
     edge-slot construction fails raises IndexError as CsrBatch does, when that batch is asked for.
 
     ccn_chunk(idx, task) enqueues hgnn_pack_ccn_chunk (csrc/ccn_pack.hip): the padded (X, A + I, n_batch, y) chunk

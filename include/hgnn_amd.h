@@ -285,8 +285,9 @@ int hgnn_net_backward_csr(const hgnn_net_config* cfg, const hgnn_csr_batch* batc
  * (nodes, f_in) fp32, adj_off (graphs + 1) int64, adj_ij (adj_nnz, 2) int32 local (i, j) in strictly
  * ascending row-major order per graph, adj_w (adj_nnz) fp32, targets (not read here).
  *
- * One workgroup builds one graph in LDS; supported per graph: n <= 32 nodes, m = nnz(A) <= 72 edge
- * slots (dual), J <= 3.  hgnn_pack_count runs the builder in its counting mode over the whole pack, once
+ * One workgroup builds one graph in LDS; J <= 3, and supported per graph: with dual, n <= 32 nodes and
+ * m = nnz(A) <= 72 edge slots; without dual (the node-graph family W, WT, x alone) n <= 64 nodes, any
+ * nnz(A).  hgnn_pack_count runs the builder in its counting mode over the whole pack, once
  * per (pack, J, dual), and writes one record of HGNN_PACK_COUNT_WORDS int32 per graph:
  *   {n, m (0 without dual), nnz[W, WT, WL, WLT, PN, PE], flags, 0}
  * A flagged graph's record holds no counts.  The caller reads the records back once, gathers those of a
@@ -297,10 +298,12 @@ int hgnn_net_backward_csr(const hgnn_net_config* cfg, const hgnn_csr_batch* batc
  * the per-graph build.  d_counts are the records hgnn_pack_count wrote for this view, J and dual; d_idx
  * (bs) int32 the batch's graph indices (repeats allowed).  If the records of d_idx do not add up to
  * `layout`, an index is outside the pack or a record is flagged, nothing but zeros and offsets is
- * written (the kernels never write past the layout).
+ * written (the kernels never write past the layout).  Without dual, a batch whose largest graph
+ * (layout->nmax) has at most 32 nodes is built by the same kernel as a dual batch's node family; a
+ * larger one by the 64-node instantiation.  The records do not depend on which of them counted.
  * ---------------------------------------------------------------------- */
 #define HGNN_PACK_COUNT_WORDS 10
-#define HGNN_PACK_FLAG_BOUNDS 1 /* n outside [1, 32] or m > 72: the host batcher takes it          */
+#define HGNN_PACK_FLAG_BOUNDS 1 /* the host batcher takes it.  dual: n not in [1, 32] or m > 72; else n not in [1, 64] */
 #define HGNN_PACK_FLAG_INDEX 2  /* the edge-slot index error (hgnn_csr_batch_plan: HGNN_ERR_INDEX) */
 #define HGNN_PACK_FLAG_COO 4    /* an index >= n, or entries not strictly ascending row-major      */
 typedef struct hgnn_pack_view {
