@@ -789,7 +789,11 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
                                                        C2Grad gd, float* __restrict__ ppart,
                                                        float* __restrict__ g0) {
     constexpr int MAXN = CCN_BIGD;
-    __shared__ float sdq1[MAXN * CM], sdq3[MAXN * CM], sdtot[CM], sdd3[CM];
+    __shared__ float sdq1[MAXN * CM], sdq3[MAXN * CM];
+    // the sums whose rounding error does not average out are summed in fp64: dq1[a] and dtot reach whole rows / every
+    // entry (the node's G[a] carries them m_a^2 times), dd3 every diagonal one; the bias partial and G[a] are single
+    // long sums.  On a star's hub (n = 130) fp32 sums and LDS float atomics here left dX 34 ulp off.
+    __shared__ double sdtot[CM], sdd3[CM], redb[4], strd[4][HM];
     __shared__ float red[4][10 * CM];
     __shared__ float sw[HM * 18 * CM];
     const int i = blockIdx.x;
@@ -802,13 +806,11 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
     const int K = 18 * cin;
     float* pp = ppart + (long long)i * (h * K + h);
     for (int t = threadIdx.x; t < h * K; t += 256) sw[t] = W[t];
-    for (int t = threadIdx.x; t < n * CM; t += 256) sdq1[t] = sdq3[t] = 0.f;
-    if (threadIdx.x < cin) sdtot[threadIdx.x] = sdd3[threadIdx.x] = 0.f;
     // parameter partials: dW[o][q*C + c] = sum_xy dpre[x][y][o] * block_q[x][y][c]
     // distinct blocks: 0 (n Sc; also 6..14), 1 q1, 2 n Sa, 3 q3, 4 tot (diag), 5 Sc, 15 D1, 16 D2^T, 17 d3 (diag)
     for (int o = 0; o < h; ++o) {
         float acc[9][CM];
-        float sb = 0.f;
+        double sb = 0.0;
 #pragma unroll
         for (int q = 0; q < 9; ++q)
 #pragma unroll
@@ -843,8 +845,8 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
                 const float t = wave_sum(acc[q][c]);
                 if (lane == 0) red[wv][q * CM + c] = t;
             }
-        sb = wave_sum(sb);
-        if (lane == 0) red[wv][9 * CM] = sb;
+        sb = wave_sum_d(sb);
+        if (lane == 0) redb[wv] = sb;
         __syncthreads();
         for (int t = threadIdx.x; t < 18 * cin; t += 256) {
             const int q = t / cin, c = t % cin;
@@ -852,9 +854,60 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
             pp[o * K + q * cin + c] = red[0][d * CM + c] + red[1][d * CM + c] + red[2][d * CM + c] +
                                       red[3][d * CM + c];
         }
-        if (threadIdx.x == 0) pp[h * K + o] = red[0][9 * CM] + red[1][9 * CM] + red[2][9 * CM] +
-                                              red[3][9 * CM];
+        if (threadIdx.x == 0) pp[h * K + o] = (float)((redb[0] + redb[1]) + (redb[2] + redb[3]));
         __syncthreads();
+    }
+    // q1 / q3 receive the row sums of dpre and tot / d3 its trace (g_q is linear in dpre): wave per row, fp64 sums,
+    // then the h-term projections  dq1[x] = W1^T rdp[x], dq3[x] = W3^T rdp[x], dtot = W4^T tr, dd3 = W17^T tr
+    {
+        double tr[HM];
+#pragma unroll
+        for (int o = 0; o < HM; ++o) tr[o] = 0.0;
+        for (int x = wv; x < n; x += 4) {
+            double rs[HM];
+#pragma unroll
+            for (int o = 0; o < HM; ++o) rs[o] = 0.0;
+            for (int y = lane; y < n; y += 64) {
+                const long long r = o2 + (long long)x * n + y;
+#pragma unroll
+                for (int o = 0; o < HM; ++o) {
+                    if (o >= h) break;
+                    const double dp = F[r * h + o] > 0.f ? (double)dF[r * h + o] : 0.0;
+                    rs[o] += dp;
+                    if (y == x) tr[o] += dp;
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < HM; ++o)
+                if (o < h) rs[o] = wave_sum_d(rs[o]);
+            if (lane < cin) {
+                double s1 = 0.0, s3 = 0.0;
+#pragma unroll
+                for (int o = 0; o < HM; ++o) {
+                    if (o >= h) break;
+                    s1 += (double)sw[o * K + cin + lane] * rs[o];
+                    s3 += (double)sw[o * K + 3 * cin + lane] * rs[o];
+                }
+                sdq1[x * CM + lane] = (float)s1;
+                sdq3[x * CM + lane] = (float)s3;
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < HM; ++o) {
+            const double t = wave_sum_d(tr[o]);
+            if (lane == 0) strd[wv][o] = t;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < cin) {
+            double t4 = 0.0, t17 = 0.0;
+            for (int o = 0; o < h; ++o) {
+                const double t = (strd[0][o] + strd[1][o]) + (strd[2][o] + strd[3][o]);
+                t4 += (double)sw[o * K + 4 * cin + threadIdx.x] * t;
+                t17 += (double)sw[o * K + 17 * cin + threadIdx.x] * t;
+            }
+            sdtot[threadIdx.x] = t4;
+            sdd3[threadIdx.x] = t17;
+        }
     }
     // input-side gradients of the contraction blocks: g_q = W_q^T dpre
     for (int e = threadIdx.x; e < n * n; e += 256) {
@@ -881,12 +934,6 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
             gd.dSa[r * cin + c] = nf * g[2];
             gd.dD1[r * cin + c] = g[15];
             gd.dD2[(o2 + y * n + x) * cin + c] = g[16];
-            atomicAdd(&sdq1[x * CM + c], g[1]);
-            atomicAdd(&sdq3[x * CM + c], g[3]);
-            if (x == y) {
-                atomicAdd(&sdtot[c], g[4]);
-                atomicAdd(&sdd3[c], g[17]);
-            }
         }
     }
     __syncthreads();
@@ -895,10 +942,10 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
         const long long r = o2 + e;
         for (int c = 0; c < cin; ++c) {
             gd.dSc[r * cin + c] += sdq1[a * CM + c];                 // q1[a] = sum_b Sc[a][b]
-            gd.dSa[r * cin + c] += sdq3[a * CM + c] + sdtot[c];      // q3[b] = sum_z Sa[b][z]; tot: every entry
+            gd.dSa[r * cin + c] += sdq3[a * CM + c] + (float)sdtot[c];  // q3[b] = sum_z Sa[b][z]; tot: every entry
         }
     }
-    if (threadIdx.x < cin) gd.dd3[(long long)i * cin + threadIdx.x] = sdd3[threadIdx.x];
+    if (threadIdx.x < cin) gd.dd3[(long long)i * cin + threadIdx.x] = (float)sdd3[threadIdx.x];
     if (!g0) return;
     // Level 0 (F_0[j] = X[j] tiled): dX[j] needs only the sum of dT_i[a_j][b][z] over the valid (b, z),
     // so node i reduces its own gradient matrices per neighbour a (coalesced, L2-hot) instead of
@@ -924,22 +971,22 @@ __global__ void __launch_bounds__(256) k_ccn2_bwd_node_big(CcnPlanView v, const 
         for (int a = wv; a < n; a += 4) {
             const bool va = mbit(vmb[a], a);
             const float mf = (float)smc[a];
-            float t = 0.f;
+            double t = 0.0;  // up to n^2 / 64 terms a lane: fp64, or the hub of a star loses ~sqrt(n) ulp here
             for (int b = lane; b < n; b += 64) {
                 if (!mbit(vmb[a], b)) continue;
                 const long long rab = (o2 + (long long)a * n + b) * cin + c;
-                t += mf * gd.dSc[rab] + gd.dD1[rab] + (va ? gd.dD2[rab] : 0.f);
+                t += (double)mf * (double)gd.dSc[rab] + (double)gd.dD1[rab] + (va ? (double)gd.dD2[rab] : 0.0);
                 for (int w = 0; w < nw; ++w) {
                     unsigned long long zs = vmb[a][w];
                     while (zs) {
                         const int z = w * 64 + __ffsll((long long)zs) - 1;
                         zs &= zs - 1ull;
-                        t += gd.dSa[(o2 + (long long)b * n + z) * cin + c];
+                        t += (double)gd.dSa[(o2 + (long long)b * n + z) * cin + c];
                     }
                 }
             }
-            t = wave_sum(t);
-            if (lane == 0) g0[(o1 + a) * cin + c] = t + (va ? sdd3[c] : 0.f);
+            t = wave_sum_d(t);
+            if (lane == 0) g0[(o1 + a) * cin + c] = (float)(t + (va ? sdd3[c] : 0.0));
         }
 }
 

@@ -106,12 +106,14 @@ def ccn_forward(p, X, adj, order, layers):
     return _linear(p, "fc", torch.cat(summed, 0))
 
 
-def ccn2_forward_closed(p, X, adj, layers):
+def ccn2_forward_closed(p, X, adj, layers, taps=None):
     """CCN_2D forward for one graph with collapse6to3(T (x) chi_ii) in its O(n^3 C) closed form
     (utils_ccn.py:281-300, contraction.py:106-121): the same function as
     ccn_forward(..., order=2) without the d^5 intermediate, so it runs at SBM N = 200 (config 5),
     which the reference itself cannot (5.65 GB per node).  Pinned against ccn_forward on small
-    graphs by tests/test_oracle.py; vectorised per node, any dtype (fp64 for parity)."""
+    graphs by tests/test_oracle.py; vectorised per node, any dtype (fp64 for parity).
+    taps: a list that receives, per level, every node's pre-activations (before the ReLU) as one flat
+    detached tensor, nodes ascending; the forward itself is unchanged by it."""
     n_nodes = X.shape[0]
     nbrs = [torch.nonzero(adj[i] > 0).view(-1) for i in range(n_nodes)]
     deg = [len(v) for v in nbrs]
@@ -120,11 +122,13 @@ def ccn2_forward_closed(p, X, adj, layers):
         idx[j, nbrs[j]] = torch.arange(deg[j])
     F = [X[i].view(1, 1, -1).expand(deg[i], deg[i], -1) for i in range(n_nodes)]
     levels = [F]
-    dmax = max(deg) if deg else 0
+    dg = torch.tensor(deg, dtype=torch.long)
+    off2 = torch.cumsum(dg * dg, 0) - dg * dg            # row offset of node j's d_j x d_j block
     for l in range(layers):
-        new = []
-        # (nodes, dmax, dmax, C) zero-padded, autograd through it
-        Fp = torch.stack([Fn.pad(f, (0, 0, 0, dmax - f.shape[1], 0, dmax - f.shape[0])) for f in F], 0)
+        new, pres = [], []
+        # every node's rows in one ragged (sum d^2, C) tensor (a star's hub beside its leaves costs
+        # d^2 + 4 d rows, not nodes x dmax^2), autograd through it
+        Ff = torch.cat([f.reshape(deg[j] * deg[j], -1) for j, f in enumerate(F)], 0)
         for i in range(n_nodes):
             n = deg[i]
             J = nbrs[i]
@@ -132,7 +136,8 @@ def ccn2_forward_closed(p, X, adj, layers):
             q = P.clamp(min=0)
             valid = (P >= 0).to(X.dtype)
             # T[a][b][c] = F_{j_a}[p_a(b)][p_a(c)], 0 where either position is absent
-            T = Fp[J.view(-1, 1, 1), q.unsqueeze(2), q.unsqueeze(1)] * (valid.unsqueeze(2) * valid.unsqueeze(1)).unsqueeze(-1)
+            rows = off2[J].view(-1, 1, 1) + q.unsqueeze(2) * dg[J].view(-1, 1, 1) + q.unsqueeze(1)
+            T = Ff[rows] * (valid.unsqueeze(2) * valid.unsqueeze(1)).unsqueeze(-1)
             Sc = T.sum(2)                                 # [a][b]
             Sa = T.sum(0)                                 # [b][c]
             q1 = Sc.sum(1)                                # [a]
@@ -149,18 +154,23 @@ def ccn2_forward_closed(p, X, adj, layers):
                        T[ar, :, ar].transpose(0, 1),      # q16[x][y] = T[y][x][y]
                        eye * d3]
             coll = torch.cat(blocks, 2)                   # (n, n, 18 C), channel q * C + ch
-            new.append(Fn.relu(_linear(p, "w{}".format(l + 1), coll)))
+            pre = _linear(p, "w{}".format(l + 1), coll)
+            pres.append(pre.detach().reshape(-1))
+            new.append(Fn.relu(pre))
+        if taps is not None:
+            taps.append(torch.cat(pres) if pres else X.new_zeros(0))
         F = new
         levels.append(F)
     summed = [sum(v.sum(0).sum(0) for v in f) for f in levels]
     return _linear(p, "fc", torch.cat(summed, 0))
 
 
-def ccn1_forward_vec(p, X, adj, layers):
+def ccn1_forward_vec(p, X, adj, layers, taps=None):
     """CCN_1D forward for one graph, vectorised per node: the same function as
     ccn_forward(..., order=1) (utils_ccn.py:185-222, 242-252, 303-324) with the chi position maps
     from one dense index table instead of per-pair Python dicts, so it runs on SBM graphs of
-    N = 400-1000 (degrees ~70-200).  Pinned against ccn_forward by tests/test_oracle.py."""
+    N = 400-1000 (degrees ~70-200).  Pinned against ccn_forward by tests/test_oracle.py.
+    taps: as in ccn2_forward_closed."""
     n_nodes = X.shape[0]
     nbrs = [torch.nonzero(adj[i] > 0).view(-1) for i in range(n_nodes)]
     deg = [len(v) for v in nbrs]
@@ -169,15 +179,21 @@ def ccn1_forward_vec(p, X, adj, layers):
         idx[j, nbrs[j]] = torch.arange(deg[j])
     F = [X[i].view(1, -1).expand(deg[i], -1) for i in range(n_nodes)]
     levels = [F]
+    dg = torch.tensor(deg, dtype=torch.long)
+    off1 = torch.cumsum(dg, 0) - dg                            # row offset of node j's d_j rows
     for l in range(layers):
-        new = []
-        Fp = torch.nn.utils.rnn.pad_sequence(F, batch_first=True)  # (nodes, dmax, C), autograd through it
+        new, pres = [], []
+        Ff = torch.cat(list(F), 0)                             # ragged (sum d, C), autograd through it
         for i in range(n_nodes):
             J = nbrs[i]
             P = idx[J][:, J]                                   # P[a][x] = position of nbr_i[x] in nbr_{j_a}
-            T = Fp[J.view(-1, 1), P.clamp(min=0)] * (P >= 0).to(X.dtype).unsqueeze(2)   # (d, d, C): T[a][x]
+            T = Ff[off1[J].view(-1, 1) + P.clamp(min=0)] * (P >= 0).to(X.dtype).unsqueeze(2)   # (d, d, C): T[a][x]
             coll = torch.cat([T.sum(0), T.sum(1)], 1)
-            new.append(Fn.relu(_linear(p, "w{}".format(l + 1), coll)))
+            pre = _linear(p, "w{}".format(l + 1), coll)
+            pres.append(pre.detach().reshape(-1))
+            new.append(Fn.relu(pre))
+        if taps is not None:
+            taps.append(torch.cat(pres) if pres else X.new_zeros(0))
         F = new
         levels.append(F)
     summed = [sum(v.sum(0) for v in f) for f in levels]

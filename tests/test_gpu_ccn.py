@@ -440,6 +440,83 @@ def test_ccn1_small_graph_path_equals_general_path(f, h, layers, bs):
         assert dxs[b, x.shape[0]:].abs().max().item() == 0.0 if x.shape[0] < X.shape[1] else True
 
 
+def _bound_batch(nmax, f, p, seed):
+    """Three graphs, the first with exactly nmax nodes (G(nmax, p) with self loops), random signed features."""
+    import ccn_edge_util as EU
+    g = torch.Generator().manual_seed(seed)
+    adjs = [EU.er(nmax, p, seed), EU.er(nmax // 2 + 1, 2 * p, seed + 1), EU.path_chords(5, seed + 2)]
+    return [(torch.randn(a.shape[0], f, generator=g), a, None) for a in adjs]
+
+
+@pytest.mark.parametrize("f,h,nmax", [(8, 8, 26), (2, 1, 64)])
+def test_ccn1_small_graph_path_at_its_bounds(f, h, nmax):
+    """The small CCN-1D path at its support bounds (csrc/ccn_small.hip cs_ok: f_in, hidden <= 8, nmax <= 64 and the
+    LDS request of cs_lds_bytes, which grows with nmax^2 (h L + 2 max(f, h) + 2 h)): f_in = hidden = 8 fits up to
+    nmax = 26, and nmax = 64 fits (f_in, hidden, layers) = (2, 1, 2) only -- (8, 8, 2) at nmax = 64 is refused.
+    Both corners against the general path -- outputs and dX bit-identical, weight gradients on the gradient bound
+    -- and the fp64 oracle; one past each bound the predicate refuses."""
+    from hgnn_amd.ccn import CcnSpec
+    from models.compnets.model_ccn import CCN_1D
+    from oracle import ref_ccn as RC
+    layers, bs = 2, 3
+    graphs = _bound_batch(nmax, f, 0.15, 10 * nmax)
+    net = CCN_1D(f, 2, h, layers)
+    fu.det_init(net, 648 + nmax)
+    p64 = {n: v.detach().double().clone().requires_grad_(True) for n, v in net.named_parameters()}
+    net = net.cuda()
+    X, A, nb = _pad(graphs, "cuda")
+    assert X.shape[1] == nmax and net._spec().small(bs, nmax) is not None
+    for args, n1 in (((1, 8, 8, 2, 2), 27), ((1, 9, 8, 2, 2), 26), ((1, 8, 9, 2, 2), 26), ((1, 8, 8, 2, 2), 64),
+                     ((1, 2, 1, 2, 2), 65), ((1, 3, 1, 2, 2), 64), ((1, 2, 2, 2, 2), 64), ((1, 2, 1, 3, 2), 64)):
+        assert CcnSpec(*args).small(bs, n1) is None, (args, n1)
+    w = torch.randn(bs, 2, generator=torch.Generator().manual_seed(bs)).cuda()
+    os_, dxs, gs = _run_path(True, net, X, A, nb, w)
+    og, dxg, gg = _run_path(False, net, X, A, nb, w)
+    assert torch.equal(os_, og), f"outputs differ: {(os_ - og).abs().max().item():.3g}"
+    assert torch.equal(dxs, dxg), f"dX differs: {(dxs - dxg).abs().max().item():.3g}"
+    for n in gg:
+        _grad_close(gs[n], gg[n], f"small vs general grad {n}")
+    for b, (x, a, _) in enumerate(graphs):
+        xr = x.double().requires_grad_(True)
+        ref = RC.ccn1_forward_vec(p64, xr, a.double(), layers)
+        _close(os_[b], ref, f"small path graph {b}")
+        (ref * w[b].double().cpu()).sum().backward()
+        _grad_close(dxs[b, :x.shape[0]], xr.grad, f"small path dX graph {b}")
+        assert x.shape[0] == X.shape[1] or dxs[b, x.shape[0]:].abs().max().item() == 0.0
+
+
+def test_ccn2_small_graph_path_at_its_bounds():
+    """The small CCN-2D path at f_in = 8, hidden = 2 and nmax = 32 (csrc/ccn2_small.hip ccn2_small_ok) against the
+    general path, bit for bit, and the closed-form fp64 oracle; one past each bound the predicate refuses."""
+    from hgnn_amd.ccn import CcnSpec
+    from models.compnets.model_ccn import CCN_2D
+    from oracle import ref_ccn as RC
+    f, h, layers, bs = 8, 2, 2, 3
+    graphs = _bound_batch(32, f, 0.25, 320)
+    net = CCN_2D(f, 2, h, layers)
+    fu.det_init(net, 328)
+    p64 = {n: v.detach().double().clone().requires_grad_(True) for n, v in net.named_parameters()}
+    net = net.cuda()
+    X, A, nb = _pad(graphs, "cuda")
+    assert X.shape[1] == 32 and net._spec().small(bs, 32) is not None
+    for spec, nmax in ((CcnSpec(2, 9, 2, 2, 2), 32), (CcnSpec(2, 8, 3, 2, 2), 32), (CcnSpec(2, 8, 2, 2, 2), 33)):
+        assert spec.small(bs, nmax) is None, (spec.f_in, spec.hidden, nmax)
+    w = torch.randn(bs, 2, generator=torch.Generator().manual_seed(bs)).cuda()
+    os_, dxs, gs = _run_path(True, net, X, A, nb, w)
+    og, dxg, gg = _run_path(False, net, X, A, nb, w)
+    assert torch.equal(os_, og), f"outputs differ: {(os_ - og).abs().max().item():.3g}"
+    assert torch.equal(dxs, dxg), f"dX differs: {(dxs - dxg).abs().max().item():.3g}"
+    for n in gg:
+        assert torch.equal(gs[n], gg[n]), f"grad {n} differs: {(gs[n] - gg[n]).abs().max().item():.3g}"
+    for b, (x, a, _) in enumerate(graphs):
+        xr = x.double().requires_grad_(True)
+        ref = RC.ccn2_forward_closed(p64, xr, a.double(), layers)
+        _close(os_[b], ref, f"small path graph {b}")
+        (ref * w[b].double().cpu()).sum().backward()
+        _grad_close(dxs[b, :x.shape[0]], xr.grad, f"small path dX graph {b}")
+        assert x.shape[0] == X.shape[1] or dxs[b, x.shape[0]:].abs().max().item() == 0.0
+
+
 def test_ccn1_small_graph_path_per_graph_drop_in():
     """net(X, A + I) per graph (n_batch None: the small path without any index tensor) equals the
     batched general path row by row; the input gradient of the per-graph call as well."""

@@ -216,6 +216,7 @@ def test_oracle_ccn2_closed_form_matches_literal(golden):
         xb = X.double().requires_grad_(True)
         a = RC.ccn_forward(pa, xa, A.double(), 2, 2)
         b = RC.ccn2_forward_closed(pb, xb, A.double(), 2)
+        assert torch.equal(RC.ccn2_forward_closed(pb, xb, A.double(), 2, taps=[]), b)  # taps change nothing
         assert torch.allclose(a, b, rtol=1e-12, atol=1e-10), (k, a, b)
         a.sum().backward()
         b.sum().backward()
@@ -239,6 +240,7 @@ def test_oracle_ccn1_vectorised_matches_literal(golden):
         xb = X.double().requires_grad_(True)
         a = RC.ccn_forward(pa, xa, A.double(), 1, 2)
         b = RC.ccn1_forward_vec(pb, xb, A.double(), 2)
+        assert torch.equal(RC.ccn1_forward_vec(pb, xb, A.double(), 2, taps=[]), b)  # taps change nothing
         assert torch.allclose(a, b, rtol=1e-12, atol=1e-10), (k, a, b)
         a.sum().backward()
         b.sum().backward()
