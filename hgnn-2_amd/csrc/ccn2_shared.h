@@ -1,4 +1,4 @@
-// Device helpers shared by the general CCN-2D kernels (ccn.hip) and the one-workgroup-per-graph CCN-2D
+// Device helpers shared by the general CCN-2D kernels (ccn2.hip) and the one-workgroup-per-graph CCN-2D
 // kernels (ccn2_small.hip): the combined contraction weights, the wave-uniform neighbour walk and the
 // parameter-partial layout.  One definition, so both paths do the same arithmetic in the same order.
 #pragma once

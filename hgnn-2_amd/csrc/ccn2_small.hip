@@ -2,7 +2,7 @@
 //
 // The reference's driver runs CCN_2D one graph per step (scripts/train_ccn.py:31-73: net(X, A + I), loss,
 // backward, an optimizer step), and a QM9 graph has at most 29 nodes of degree ~2-6.  The general path
-// (ccn.hip) spends such a call on dispatches: 3 plan kernels, pack, a level kernel per layer, two readout
+// (ccn*.hip) spends such a call on dispatches: 3 plan kernels, pack, a level kernel per layer, two readout
 // kernels forward; the readout backward, per level a node pass, a parameter reduction and a gather, and an
 // unpack backward.  Here one 512-thread workgroup per graph
 //   * builds the receptive fields in LDS (row bit sets of the adjacency, utils_ccn.py:159-163; degrees,

@@ -2,7 +2,7 @@
 //
 // The reference's driver calls the network one graph at a time (scripts/train_ccn.py:31-73: net(X, A + I),
 // loss, backward and an optimizer step per graph), and QM9 graphs have at most 29 nodes: there the general
-// path (ccn.hip) spends the call on dispatches, not arithmetic (5 plan + 5 forward + 9 backward launches,
+// path (ccn*.hip) spends the call on dispatches, not arithmetic (5 plan + 5 forward + 9 backward launches,
 // ~0.18 ms of GPU time and more of host time per graph).  Here one workgroup per graph
 //   * builds the receptive fields in LDS: row bit sets over the graph's nodes (utils_ccn.py:195-199,
 //     nbr_i = ascending nonzero(adj[i])), degrees, row offsets, and reads every chi position by popcount

@@ -4,7 +4,7 @@ The reference builds every receptive field, chi matrix, promotion and the
 d^5 tensor product per node in Python (functions/utils_ccn.py:66-324,
 functions/contraction.py:106-121) and runs one graph per forward
 (models/compnets/model_ccn.py:41-64, 93-105).  Here a whole padded batch of
-graphs goes through three device phases (csrc/ccn.hip):
+graphs goes through three device phases (csrc/ccn.hip, the executor, names the files of the kernels):
 
   plan      neighbour lists, degrees, prefix offsets and chi position maps
             (int, bit-exact with _get_chi) -- one small host sync for the
@@ -33,8 +33,8 @@ from .net import (_capturing, _require_cuda, _f32, _i64, _raise_bits, check_erro
 SMALL = os.environ.get("HGNN_CCN_SMALL", "1") != "0"
 SMALL2_WS_CAP = 512 << 20  # bytes: the CCN-2D small path's workspace bound per call (CcnSpec.small)
 
-CCN_MAX_DEGREE = {1: 1024, 2: 256}  # csrc/ccn.hip CCN1_MAXD, CCN_BIGD (by order)
-CCN2_MAX_CHANNELS = 16  # csrc/ccn.hip C2_CMAX_WIDE: CCN-2D f_in and hidden
+CCN_MAX_DEGREE = {1: 1024, 2: 256}  # csrc/ccn_general.h CCN1_MAXD, CCN_BIGD (by order)
+CCN2_MAX_CHANNELS = 16  # csrc/ccn_general.h C2_CMAX_WIDE: CCN-2D f_in and hidden
 
 
 class CcnSpec:

@@ -1,6 +1,6 @@
-"""Inputs, case tables, the dispatch mirror and the checks of tests/test_gpu_ccn_edges.py (the general CCN path of
-csrc/ccn.hip at its kernel-selection and degree boundaries); tests/test_ccn_edge_inputs.py checks all of it on the
-CPU.  Nothing here needs a GPU except run_gpu() and plan_maps_gpu().
+"""Inputs, case tables, the dispatch mirror and the checks of tests/test_gpu_ccn_edges.py (the general CCN path,
+csrc/ccn.hip and the files it names, at its kernel-selection and degree boundaries); tests/test_ccn_edge_inputs.py
+checks all of it on the CPU.  Nothing here needs a GPU except run_gpu() and plan_maps_gpu().
 
 Reference of every comparison: oracle/ref_ccn.py (ccn2_forward_closed / ccn1_forward_vec) in fp64, with the same
 oracle in fp32 as the naive leg.  The kernel's rms and max error against fp64 may be at most FACTOR = 2 x the naive
@@ -27,13 +27,13 @@ from oracle import ref_ccn as RC
 FACTOR = 2.0          # oracle/parity.py: the fp64-leg factor
 MARGIN_M = 100.0      # family M: min |pre64| / max |pre32 - pre64| per level
 
-# csrc/ccn.hip constants the mirror restates
-CCN_MAXD, CCN_BIGD, CCN1_MAXD = 64, 256, 1024      # ccn.hip:29-36
-C1F = C1H = 8                                      # ccn.hip:37
-C2_CMAX = C2_HMAX = 8                              # ccn.hip:471-472
-C2_NCAP = 64                                       # ccn.hip:498
-RO_CH = 32                                         # ccn.hip:1900
-ASYNC_PLAN_BOUND = {1: 8 << 20, 2: 1 << 20}        # hgnn_amd/ccn.py:84
+# csrc/ccn_general.h constants the mirror restates
+CCN_MAXD, CCN_BIGD, CCN1_MAXD = 64, 256, 1024
+C1F = C1H = 8
+C2_CMAX = C2_HMAX = 8
+C2_NCAP = 64
+RO_CH = 32
+ASYNC_PLAN_BOUND = {1: 8 << 20, 2: 1 << 20}        # hgnn_amd/ccn.py ASYNC_PLAN_BOUND
 
 
 # ---------------------------------------------------------------------------------------------- graphs
@@ -408,56 +408,56 @@ def check(name, got, tag=""):
 
 # ---------------------------------------------------------------------------------------------- dispatch mirror
 def auto_plan(order, bs, nmax):
-    """hgnn_amd/ccn.py:87-93"""
+    """hgnn_amd/ccn.py _plan"""
     return "async" if bs * nmax ** 3 <= ASYNC_PLAN_BOUND[order] else "sync"
 
 
 def ro_chunks(rows, bs):
-    """ccn.hip:1901-1905"""
+    """ccn_readout.hip ro_chunks"""
     per = rows // bs if bs > 0 else rows
     return min(per // 4096 + 1, RO_CH)
 
 
 def mirror(order, f, h, layers, degs, bs, nmax, plan):
-    """The kernels and branches hgnn_ccn_forward / hgnn_ccn_backward (ccn.hip:2438-2597) select for a batch whose
+    """The kernels and branches hgnn_ccn_forward / hgnn_ccn_backward (ccn.hip) select for a batch whose
     graphs have the degree arrays `degs` (one per slot), as a set of names."""
     alld = np.concatenate([np.asarray(d, np.int64) for d in degs]) if degs else np.zeros(0, np.int64)
     dmax = int(alld.max()) if alld.size else 0
-    if plan == "async":  # ccn.hip:2399-2404: bounds from the shape
+    if plan == "async":  # ccn_plan.hip ccn_plan: bounds from the shape
         s0, s2, s3 = bs * nmax * nmax, bs * nmax, nmax
-    else:                # ccn.hip:2389-2397: the device totals
+    else:                # ccn_plan.hip ccn_plan: the device totals
         s0, s2, s3 = int(alld.sum()), int(alld.size), dmax
     names = {f"plan[{plan}]"}
     if order == 2:
-        big = s3 > CCN_MAXD                                           # ccn.hip:2466, 2528
+        big = s3 > CCN_MAXD                                           # ccn.hip CcnRun::bigd
         for d in (64, 65, 256):
             if (alld == d).any():
                 names.add(f"c2[deg={d}]")
         if big and dmax <= CCN_MAXD:
             names.add("c2[big kernels over zero nodes]")
-        names.add("k_ccn_bcast" if big else "top_direct")             # ccn.hip:2529-2534
+        names.add("k_ccn_bcast" if big else "top_direct")             # ccn.hip ccn2_backward
         for l in range(layers):
             cin = f if l == 0 else h
-            narrow = cin <= C2_CMAX and h <= C2_HMAX                  # ccn.hip:2462, 2544
-            if l == 0:                                                # ccn.hip:2267-2270, 2292-2296
+            narrow = cin <= C2_CMAX and h <= C2_HMAX                  # ccn_general.h c2_big_select
+            if l == 0:                                                # ccn_general.h c2_select, level 0
                 t = "8,2,1,true" if cin <= 8 else "16,2,1,true"
                 names |= {f"k_c2_fwd<{t}>", f"k_c2_bwd<{t}>", "k_ccn2_dx0[cin>8]" if cin > 8 else "k_ccn2_dx0"}
-            else:                                                     # ccn.hip:2271-2273, 2297-2301
+            else:                                                     # ccn_general.h c2_select, levels >= 1
                 t = "2,2,8,false" if cin <= 2 else "8,2,4,false" if cin <= 8 else "16,2,2,false"
                 tb = t if cin <= 8 else "16,1,2,false"
                 names |= {f"k_c2_fwd<{t}>", f"k_c2_bwd<{tb}>", f"c2_level[cin={cin}]"}
-                g = "2,8" if h <= 2 else "8,1" if h <= 8 else "16,1"  # ccn.hip:2307-2312
+                g = "2,8" if h <= 2 else "8,1" if h <= 8 else "16,1"  # ccn_general.h c2_gather_select
                 names |= {f"k_c2_gather<{g}>", f"k_c2_gather<{g}>[h={h}]"}
-                if s3 > C2_NCAP:                                      # ccn.hip:2314-2325
+                if s3 > C2_NCAP:                                      # ccn.hip ccn2_backward
                     names.add("k_c2_gather_big<%s>" % ("2,4" if h <= 2 else g))
-            if big:                                                   # ccn.hip:2466-2475, 2547-2560
+            if big:                                                   # ccn.hip ccn2_forward, ccn2_backward
                 t = "8,8" if narrow else "16,16"
                 names |= {f"k_ccn2_fwd_big<{t}>", f"k_ccn2_bwd_node_big<{t}>", "k_c2_dp_big"}
-        names.add(f"readout[nch={ro_chunks(s2, bs)}]")               # ccn.hip:2494: nodes
+        names.add(f"readout[nch={ro_chunks(s2, bs)}]")               # ccn.hip hgnn_ccn_forward: nodes
         if f > C2_CMAX:
-            names.add("readout[f passes>1]")                          # ccn.hip:1928
+            names.add("readout[f passes>1]")                          # ccn_readout.hip k_ccn_readout_part
         if h > C2_CMAX:
-            names.add("readout[h passes>1]")                          # ccn.hip:1945
+            names.add("readout[h passes>1]")                          # ccn_readout.hip k_ccn_readout_part
     else:
         for d in (64, 65, 1024):
             if (alld == d).any():
@@ -465,14 +465,14 @@ def mirror(order, f, h, layers, degs, bs, nmax, plan):
         small, large = bool((alld <= 64).any()), bool((alld > 64).any())
         for l in range(layers):
             cin = f if l == 0 else h
-            if small:  # ccn.hip:221, 323, 394
+            if small:  # ccn1.hip: the one-chunk branch of each kernel
                 names.add("k_ccn1_fwd[fast]" if cin <= C1F else "k_ccn1_fwd[chunked,n<=64,cin>8]")
                 names.add("k_ccn1_bwd_node[fast]" if cin <= C1F and h <= C1H else
                           "k_ccn1_bwd_node[chunked,n<=64]")
                 names.add("k_ccn1_bwd_gather[fast]" if cin <= C1F else "k_ccn1_bwd_gather[chunked,n<=64,cin>8]")
             if large:
                 names |= {"k_ccn1_fwd[chunked,n>64]", "k_ccn1_bwd_node[chunked,n>64]", "k_ccn1_bwd_gather[chunked,n>64]"}
-        names.add(f"readout1[nch={ro_chunks(s0, bs)}]")              # ccn.hip:2494: sum of degrees
+        names.add(f"readout1[nch={ro_chunks(s0, bs)}]")              # ccn.hip hgnn_ccn_forward: sum of degrees
         if h > C2_CMAX:
             names.add("readout1[h passes>1]")
         if f > C2_CMAX:

@@ -34,7 +34,7 @@ def test_tiny_batch():
 
 
 def test_ro_chunks_rule():
-    """ccn.hip:1901-1905: rows per graph / 4096 + 1, capped at 32 -- the second chunk starts at 4096 rows"""
+    """ccn_readout.hip ro_chunks: rows per graph / 4096 + 1, capped at 32 -- the second chunk starts at 4096 rows"""
     assert [U.ro_chunks(r, 1) for r in (0, 4095, 4096, 4225, 8192, 10 ** 9)] == [1, 1, 2, 2, 3, 32]
     assert U.ro_chunks(3 * 4225, 3) == 2 and U.ro_chunks(4225, 2) == 1
     by = {c["graphs"][0]: U.case_mirror(c["name"]) for c in U.CASES_S if c["order"] == 1}
@@ -61,7 +61,7 @@ def test_mirror_selections():
     assert "c2[big kernels over zero nodes]" in a and "k_ccn_bcast" in a and "top_direct" in s
     assert U.auto_plan(2, 1, 64) == "async" and U.auto_plan(2, 1, 66) == "async" and U.auto_plan(2, 1, 130) == "sync"
     assert U.auto_plan(2, 7, 66) == "sync" and U.auto_plan(1, 1, 129) == "async" and U.auto_plan(1, 1, 1024) == "sync"
-    # wide levels: the backward's instantiation differs from the forward's (ccn.hip:2301)
+    # wide levels: the backward's instantiation differs from the forward's (ccn_general.h c2_select)
     s = m(2, 8, 16, 2, [np.array([3, 3, 3])], 1, 3, "async")
     assert {"k_c2_fwd<16,2,2,false>", "k_c2_bwd<16,1,2,false>", "k_c2_gather<16,1>", "readout[h passes>1]"} <= s
     # CCN-1D: 9 channels at degree <= 64 enter the chunked branch without a second chunk

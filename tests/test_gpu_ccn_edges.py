@@ -1,7 +1,7 @@
-"""The general CCN path (csrc/ccn.hip: plan kernels, CCN-1D, the k_c2_* templates, the _big kernels, the readout) at
-its kernel-selection and degree boundaries, against the fp64 oracle (oracle/ref_ccn.py) with the same oracle in fp32
-as the naive leg.  tests/ccn_edge_util.py holds the graphs, the case tables, the weight families, the mirror of the
-dispatch and the checks; tests/test_ccn_edge_inputs.py checks all of those on the CPU.
+"""The general CCN path (csrc/ccn.hip and the files it names: plan kernels, CCN-1D, the k_c2_* templates, the _big
+kernels, the readout) at its kernel-selection and degree boundaries, against the fp64 oracle (oracle/ref_ccn.py)
+with the same oracle in fp32 as the naive leg.  tests/ccn_edge_util.py holds the graphs, the case tables, the weight
+families, the mirror of the dispatch and the checks; tests/test_ccn_edge_inputs.py checks all of those on the CPU.
 
 Everything runs through forward_batch with hgnn_amd.ccn.SMALL = False.  Every case:
   * outputs, dX and each parameter gradient: the kernel's rms and max error against fp64 are each at most 2 x those
