@@ -28,6 +28,7 @@ train_epoch and eval_epoch are train_with_mnb and test_with_mnb over a data set.
 import ctypes
 import math
 import os
+import struct
 
 import torch
 
@@ -367,6 +368,11 @@ CCN2_TRAIN_FUSED_DEFAULT = True
 # profiles/ccn_train_optim_ab.json (tools/ab_ccn_train.py --optim ...): fused where the fused median is at or below
 # the unfused median.
 CCN_TRAIN_FUSED_OPTIM = {(1, "sgd"): True, (1, "adam"): True, (2, "sgd"): True, (2, "adam"): True}
+# Mini-batch mode (batch_size=B): whether fused=None takes hgnn_ccn_small_train_batch where it is supported.  From
+# profiles/ccn_train_batch_ab.json (tools/ab_ccn_train.py --batch 32 256): fused only if the fused median is at or
+# below the pieces route's at both batch sizes; otherwise the pieces route is the default and the kernels stay
+# reachable with fused=True.
+CCN_TRAIN_BATCH_FUSED_DEFAULT = True
 
 
 class CcnTrainStep(_Optimizer):
@@ -412,12 +418,44 @@ class CcnTrainStep(_Optimizer):
     fused paths are then hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt, the same kernels with their optimizer
     stage instantiated for it, and the unfused path calls hgnn_optim_step.  Routing is the same; fused=None takes
     a fused kernel for sgd / adam by CCN_TRAIN_FUSED_OPTIM, the measured default.
+
+    Mini-batches: batch_size=B (an integer >= 1; None, the default, is everything above, unchanged).  step() then
+    cuts the G graphs into consecutive mini-batches of B, the last one shorter, and takes ONE optimizer step per
+    mini-batch, its graphs in parallel and all seeing the same weights: regression -- nn.MSELoss over the (B, n_out)
+    block of outputs and normalised targets, dout = 2 (out - yn) / (B n_out), meters as TrainStep's (stats[0:2] the
+    mini-batch's MSE and MAE, stats[2:4] their RunningAverages, updated once per mini-batch); classification --
+    nn.CrossEntropyLoss on the (B, n_out) logits, dout = (softmax - onehot) / B.  The parameter gradients are summed
+    over the mini-batch's graphs; step_count grows by one per mini-batch (the bias corrections use it); a shorter last
+    mini-batch divides by its own size; an empty slot (n_b = 0) is a graph like any other (its output is fc.bias).
+    .path:
+
+      batch_fused  hgnn_ccn_small_train_batch: two dispatches per mini-batch (one workgroup per graph: forward, its
+                   dout row, backward; then one wave per parameter element: the sum over the graphs, the gradient, the
+                   optimizer update, the meters) -- CCN_1D within hgnn_ccn_small_train_batch_supported, B <= 4096
+      batch        the library's pieces per mini-batch: forward_batch, hgnn_mse_loss on the device-normalised target
+                   with (0, 1) (or hgnn_xent_loss), autograd backward, hgnn_optim_step -- CCN_2D, larger graphs, wider
+                   channels.  The same arithmetic bit for bit where both routes exist.
+
+    fused=None takes batch_fused where it is supported and CCN_TRAIN_BATCH_FUSED_DEFAULT (the measured default) says
+    so, fused=False never, fused=True raises where it is not supported, fused="ccn2" raises (there is no CCN-2D
+    mini-batch kernel).  Neither route synchronises with the host.  A graph the fused kernels reject (validation
+    bits, or a class target that is no index) makes its whole mini-batch take no step and update no meter; the other
+    graphs' out rows are written, the error shows at the next check, and step_count still counts the mini-batch (its
+    step number is consumed: the device decides, the host cannot know).
     """
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, t_mean=None, t_std=1.0,
-                 fused=None, classification=None, optimizer="adamax", momentum=0.9):
+                 fused=None, classification=None, optimizer="adamax", momentum=0.9, batch_size=None):
         from models.compnets.model_ccn import _CCN
         self._check_optimizer(optimizer)
+        if batch_size is not None and (isinstance(batch_size, bool) or not isinstance(batch_size, int)
+                                       or batch_size < 1):
+            raise RuntimeError(f"hgnn_amd: batch_size={batch_size!r}: expected None (the per-graph loop) or an "
+                               "integer >= 1")
+        if batch_size is not None and isinstance(fused, str) and fused == "ccn2":
+            raise RuntimeError("hgnn_amd: fused=\"ccn2\" with batch_size: there is no CCN-2D mini-batch kernel "
+                               "(fused=None or False runs CCN_2D mini-batches from the library's pieces)")
+        self.batch_size = batch_size
         if not isinstance(model, _CCN):
             raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
         # the reference's rule (train_ccn.py:39): mean == 0 marks generated (classification) data
@@ -458,8 +496,9 @@ class CcnTrainStep(_Optimizer):
                                "(hgnn_ccn_small_train_supported)")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
         self.out = None
-        self.path = None  # "fused", "fused2d" or "unfused": what the last step ran
+        self.path = None  # "fused", "fused2d" or "unfused" (mini-batch mode: "batch_fused" or "batch"): the last step
         self._ws2d = {}   # nmax -> the CCN-2D kernel's one-graph workspace
+        self._ws_batch = None  # hgnn_ccn_small_train_batch's workspace (sized once: it does not depend on nmax)
         self._grads = [torch.zeros_like(p) for p in self.params]
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
         # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
@@ -480,8 +519,33 @@ class CcnTrainStep(_Optimizer):
         cfg = self.spec.config(1, nmax)
         return bool(L.lib().hgnn_ccn2_small_train_supported(ctypes.byref(cfg)))
 
+    def _supported_batch(self, nmax):
+        """Whether hgnn_ccn_small_train_batch takes mini-batches of this step padded to nmax nodes."""
+        cfg = self.spec.config(1, nmax)
+        if not L.lib().hgnn_ccn_small_train_batch_supported(ctypes.byref(cfg)):
+            return False
+        # a mini-batch is one call's at most; the entry's MSE meters are hgnn_mse_loss's, which stops dividing
+        # below (float)1e-5 where the CCN rule always divides (the entry's own fp32 comparison)
+        f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]  # noqa: E731
+        return self.batch_size <= CCN_TRAIN_MAX_GRAPHS and (self.classification
+                                                            or f32(self.t_std + 1e-8) >= f32(1e-5))
+
+    def _route_batch(self, nmax):
+        """The path of a chunk padded to nmax nodes in mini-batch mode."""
+        fused = self.fused
+        if fused is None:
+            return "batch_fused" if CCN_TRAIN_BATCH_FUSED_DEFAULT and self._supported_batch(nmax) else "batch"
+        if fused:
+            if not self._supported_batch(nmax):
+                raise RuntimeError(f"hgnn_amd: fused=True, but batch_size = {self.batch_size} at nmax = {nmax} is "
+                                   "outside the mini-batch kernels' bounds (hgnn_ccn_small_train_batch_supported)")
+            return "batch_fused"
+        return "batch"
+
     def _route(self, nmax):
         """The path of a chunk padded to nmax nodes."""
+        if self.batch_size is not None:
+            return self._route_batch(nmax)
         fused = self.fused
         if fused is None:
             one = CCN_TRAIN_FUSED_OPTIM.get((1, self.optimizer), True)
@@ -522,13 +586,20 @@ class CcnTrainStep(_Optimizer):
         in index order; y: raw targets (G,) or (G, n_out) -- classification: G class indices of any dtype.
         Returns the device tensor `stats` = [loss, mae, running loss, running mae] after the last graph; leaves
         .out (G, n_out), the output each graph saw before its own update, and p.grad = the last graph's
-        gradients."""
+        gradients.
+        Mini-batch mode (batch_size=B): one step per mini-batch of B consecutive graphs, the last one shorter;
+        `stats` after the last mini-batch, .out the output each graph saw before its mini-batch's update, p.grad
+        the last mini-batch's gradients."""
         self._targets.poll(block=False)
         X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
         G, nmax = X.shape[0], X.shape[1]
         self.path = path = self._route(nmax)  # before the work: a strict check inside it may raise
         self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
-        if path == "unfused":
+        if path == "batch_fused":
+            self._step_batch_fused(X, adj, n_batch, y)
+        elif path == "batch":
+            self._step_batch_pieces(X, adj, n_batch, y)
+        elif path == "unfused":
             self._step_unfused(X, adj, n_batch, y)
         else:
             self._step_fused(X, adj, n_batch, y, two=path == "fused2d")
@@ -622,6 +693,74 @@ class CcnTrainStep(_Optimizer):
         if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
             self._targets.watch()
 
+    def _step_batch_fused(self, X, adj, n_batch, y):
+        """Mini-batch mode, hgnn_ccn_small_train_batch: one call per run of whole mini-batches within the entry's
+        4096-graph bound."""
+        from .ccn import _word
+        from .net import _capturing, check_errors, strict
+        lib = L.lib()
+        check_errors(block=False)
+        dev = X.device
+        stream = L.stream_handle(dev)
+        B, G = self.batch_size, X.shape[0]
+        if self._ws_batch is None:
+            cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, X.shape[1])
+            self._ws_batch = torch.empty(lib.hgnn_ccn_small_train_batch_workspace_bytes(ctypes.byref(cfg), B),
+                                         dtype=torch.uint8, device=dev)
+        span = CCN_TRAIN_MAX_GRAPHS // B * B
+        s1, s2 = self._states()
+        for g0 in range(0, G, span):
+            g1 = min(g0 + span, G)
+            k = -(-(g1 - g0) // B)  # mini-batches of this call: one step number each, applied or not
+            cfg = self.spec.config(g1 - g0, X.shape[1])
+            # the per-step scalars in double on the host, as hgnn_optim_step forms its own; pinned
+            sc = torch.tensor(self._step_scalars(self.step_count, k),
+                              dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
+            err, tag = _word.next(dev)
+            L.check(lib.hgnn_ccn_small_train_batch(
+                ctypes.byref(cfg), B, self._kind, int(self.classification), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]),
+                L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]), self.t_mean, self.t_std,
+                L.ptr_array(self.params), L.ptr_array(self._grads), s1, s2, L.ptr(sc), self._b1(), self.betas[1],
+                self.eps, self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), L.ptr(self._ws_batch), err,
+                tag, stream), "hgnn_ccn_small_train_batch")
+            self.step_count += k
+        for p, g in zip(self.params, self._grads):
+            p.grad = g
+        if strict() and not _capturing():
+            _word.check(True)
+
+    def _step_batch_pieces(self, X, adj, n_batch, y):
+        """Mini-batch mode from the library's own pieces, per mini-batch: forward_batch, hgnn_mse_loss on the
+        device-normalised target with (0, 1) -- n = B n_out -- or hgnn_xent_loss with n = B, autograd backward,
+        hgnn_optim_step."""
+        lib = L.lib()
+        m = self.model
+        stream = L.stream_handle(X.device)
+        cls = self.classification
+        if not cls:
+            yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device
+        n_out, B = self.spec.n_out, self.batch_size
+        for g0 in range(0, X.shape[0], B):
+            g1 = min(g0 + B, X.shape[0])
+            for p in self.params:
+                p.grad = None
+            out = m.forward_batch(X[g0:g1], adj[g0:g1], None if n_batch is None else n_batch[g0:g1])
+            dout = torch.empty_like(out)
+            if cls:
+                L.check(lib.hgnn_xent_loss(L.ptr(out.detach()), L.ptr(y[g0:g1]), g1 - g0, n_out, L.ptr(self.stats),
+                                           L.ptr(dout), L.ptr(self._targets.dev), stream), "cross-entropy loss")
+            else:
+                L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(yn[g0:g1]), (g1 - g0) * n_out, 0.0, 1.0,
+                                          L.ptr(self.stats), L.ptr(dout), stream), "mse loss")
+            torch.autograd.backward(out, dout)
+            grads = [p.grad for p in self.params]
+            if any(gr is None for gr in grads):
+                raise RuntimeError("hgnn_amd: a parameter received no gradient")
+            self._optim_step(lib, grads, stream)
+            self.out[g0:g1].copy_(out.detach())
+        if cls:  # the word is sticky: one look after the list
+            self._targets.watch()
+
     def check_targets(self):
         """Raise if a classification step or evaluation saw a target outside [0, n_outputs) (host sync): the
         unfused path's and evaluate's error word, then the fused kernel's (hgnn_amd.net.check_errors())."""
@@ -696,9 +835,14 @@ class CcnTrainStep(_Optimizer):
         """train_ccn(net, data, task, ...) (scripts/train_ccn.py:24-73): one step per graph in list order, new
         meters; returns (losses.val, error.val), read once at the end.  Classification: targets[task] is the
         class index, n_outputs >= 2, and error.val is the 0.0 the reference's untouched meter returns.
-        data: a list of instances, a GraphPack or a DevicePack (_epoch_chunks)."""
+        data: a list of instances, a GraphPack or a DevicePack (_epoch_chunks).
+        Mini-batch mode: one step per mini-batch; chunk is rounded down to a multiple of batch_size (and at least
+        to batch_size), so the mini-batches are runs of batch_size consecutive graphs of the data order whatever
+        the chunking."""
         if self.spec.n_out != 1 and not self.classification:
             raise RuntimeError("hgnn_amd: train_epoch takes one target per graph (targets[task].view(1))")
+        if self.batch_size is not None:
+            chunk = max(self.batch_size, chunk // self.batch_size * self.batch_size)
         self.reset_running()
         for X, A, nb, y in self._epoch_chunks(data, task, chunk):
             self.step(X, A, nb, y)

@@ -592,6 +592,54 @@ int hgnn_ccn2_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, co
                               float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
                               double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
                               int32_t* d_err, int32_t tag, void* stream);
+/* Mini-batch training for CCN_1D: one optimizer step per mini-batch of `batch` graphs, the graphs of a mini-batch in
+ * parallel (one workgroup each), everything on the device.  The cfg->bs graphs are cut into ceil(bs / batch)
+ * consecutive mini-batches, the last one shorter; mini-batch k + 1 runs on the weights mini-batch k left.  Per
+ * mini-batch of B graphs, all seeing the same weights: out_g = net(X_g, A_g + I); MSE: the target normalised as
+ * above, nn.MSELoss over the (B, n_out) block, dout = 2 (out - y') / (B n_out); classification: nn.CrossEntropyLoss
+ * on the (B, n_out) logits, dout = (softmax - onehot) / B; the parameter gradients summed over the B graphs; one
+ * step of the optimizer `kind`.  Two dispatches per mini-batch, ordered by the stream alone.  The arithmetic is that
+ * of the pieces on the mini-batch's slice -- hgnn_ccn_small_forward, hgnn_mse_loss on the normalised target (or
+ * hgnn_xent_loss), hgnn_ccn_small_backward, hgnn_optim_step -- bit for bit: out, every gradient, the meters, the
+ * optimizer state and the parameters.  (The running loss of the classification branch is formed from the same row
+ * losses in the same order.)
+ *   supported: host only; 1 for order 1 within hgnn_ccn_small_train_supported's bounds (cfg->bs is not looked at),
+ *     else 0 (order 2 has no mini-batch kernel).
+ *   workspace_bytes: cfg->bs reject words (a call clears and uses the first ceil(bs / batch), one per mini-batch,
+ *     with one hipMemsetAsync), then one mini-batch's per-graph regions, each 256-byte aligned: the level partials
+ *     [batch][ptot], the readout features [batch][nf] and dout [batch][n_out].  It grows with `batch` and with
+ *     cfg->bs, and a workspace sized for (bs, batch) serves every call with no more graphs and no larger
+ *     mini-batches.  The regions are reused by the mini-batches of a call in stream order; nothing in the workspace
+ *     is read before it is written, apart from the reject words.  0 where unsupported, for batch < 1 or bs outside
+ *     1 .. 4096.  The caller may keep it across calls on one stream.
+ *   cfg->bs = the number of graphs, 1 .. 4096; batch >= 1 (it may exceed bs: one mini-batch of bs graphs).
+ *   kind, xent, d_X, d_adj, d_n_batch, d_y, t_mean, t_std, params, state1, state2, the hyper-parameters, d_err and
+ *     tag: as hgnn_ccn_small_train_opt.  MSE: (float)(t_std + 1e-8) must be at least 1e-5 (HGNN_ERR_ARG below:
+ *     hgnn_mse_loss, whose meters these are, stops dividing there).
+ *   grads: left holding the last applied mini-batch's gradients.
+ *   d_steps (ceil(bs / batch), 2): the rows of hgnn_ccn_small_train_opt, but row k belongs to mini-batch k WHETHER
+ *     OR NOT it is applied: the host cannot know which mini-batches the device rejected, so a rejected mini-batch
+ *     consumes its row (and its step number) without taking the step.
+ *   d_stats[4]: as hgnn_mse_loss (or hgnn_xent_loss: [1] and [3] never written) updates them, once per applied
+ *     mini-batch: the mini-batch's loss and MAE and the RunningAverage of both.
+ *   d_out (bs, n_out): the output each graph saw before its mini-batch's update.
+ *   An empty slot (n_b = 0) is a graph like any other: its output is fc.bias, and it contributes to the loss and
+ *     to the fc.bias gradient.
+ *   A graph with validation bits (classification: or a class target that is no integer in [0, n_out)) gets its
+ *     d_out row, ORs its bits into its mini-batch's reject word and stores *d_err = tag * 256 + bits; its whole
+ *     mini-batch then takes no step: no gradients, no meters, no update (the other graphs' d_out rows are
+ *     written).  The call goes on with the next mini-batch.
+ *   Returns HGNN_ERR_UNSUPPORTED where supported is 0, HGNN_ERR_ARG for a null pointer (d_n_batch may be NULL;
+ *     SGD: state2 may be), batch < 1, bs outside 1 .. 4096, a tag outside (0, 2^23), an unknown kind, or
+ *     xent with n_out < 2.  No allocation and no synchronisation inside the entry. */
+int hgnn_ccn_small_train_batch_supported(const hgnn_ccn_config* cfg);
+size_t hgnn_ccn_small_train_batch_workspace_bytes(const hgnn_ccn_config* cfg, int batch);
+int hgnn_ccn_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, int xent, const float* d_X,
+                               const float* d_adj, const int64_t* d_n_batch, const float* d_y, double t_mean,
+                               double t_std, float* const* params, float* const* grads, float* const* state1,
+                               float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
+                               double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
+                               int32_t* d_err, int32_t tag, void* stream);
 /* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
  * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
  * as above.  One block, fp64 sums in a fixed order: the same bits every call. */

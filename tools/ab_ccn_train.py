@@ -20,7 +20,12 @@ CCN_2D(5, 2, 2, 2) on those graphs with the label g % 2, written to profiles/ccn
 --optim sgd|adam|adamax (--momentum, default 0.9): the drivers' other optimizers (scripts/main_ccn.py:155-162) on
 all three paths -- torch.optim.SGD(momentum) / Adam / Adamax, hgnn_optim_step, and the fused kernels'
 hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt (adamax: the Adamax entries).  The result is merged into
-profiles/ccn_train_optim_ab.json under the key "order<N>_<loss>_<optim>"; the files above are left alone."""
+profiles/ccn_train_optim_ab.json under the key "order<N>_<loss>_<optim>"; the files above are left alone.
+
+--batch B [B ...] (e.g. --batch 32 256): mini-batch training, CcnTrainStep(batch_size=B), on the same graphs under the
+same protocol -- the per-graph fused loop (order 2: fused2d) against, per B, the pieces route (fused=False) and, for
+order 1, the mini-batch kernels (fused=True: hgnn_ccn_small_train_batch); no torch arm.  Median, min and max ms per
+graph, merged into profiles/ccn_train_batch_ab.json under the key "order<N>_<loss>_<optim>"."""
 import argparse
 import copy
 import json
@@ -36,6 +41,45 @@ import torch  # noqa: E402
 MEAN, STD, LR = 0.3, 1.7, 1e-3
 
 
+def batch_arms(args, net, inputs, stats, optim, nmax):
+    """--batch B [B ...]: an epoch over the same graphs as mini-batches (CcnTrainStep(batch_size=B)) against the
+    per-graph fused loop, arms alternating in one process, 2 warm-up and 10 timed epochs each."""
+    from hgnn_amd.train import CcnTrainStep
+    two = args.order == 2
+    kw = dict(lr=LR, optimizer=optim, momentum=args.momentum, **stats)
+    arms = {"per_graph_fused2d" if two else "per_graph_fused":
+            CcnTrainStep(copy.deepcopy(net), fused="ccn2" if two else True, **kw)}
+    for B in args.batch:
+        arms[f"batch_pieces_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused=False, batch_size=B, **kw)
+        if not two:  # there is no CCN-2D mini-batch kernel
+            arms[f"batch_fused_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused=True, batch_size=B, **kw)
+    G = inputs[0].shape[0]
+    times = {k: [] for k in arms}
+    for it in range(12):
+        for k, st in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st.step(*inputs)
+            torch.cuda.synchronize()
+            if it >= 2:
+                times[k].append((time.perf_counter() - t0) * 1e3 / G)
+    res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5),
+                                 "max": round(max(v), 5)} for k, v in times.items()}
+    res.update(paths={k: st.path for k, st in arms.items()}, loss=args.loss, order=args.order, graphs=G, nmax=nmax,
+               epochs=len(next(iter(times.values()))), optim=optim, batch=list(args.batch))
+    print(json.dumps(res))
+    os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
+    path = os.path.join(REPO, "profiles", "ccn_train_batch_ab.json")
+    merged = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            merged = json.load(f)
+    merged[f"order{args.order}_{args.loss}_{optim}"] = res
+    with open(path, "w") as f:
+        json.dump(merged, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     import hgnn_amd.datagen as dg
     from hgnn_amd.train import CcnTrainStep
@@ -45,6 +89,7 @@ def main():
     ap.add_argument("--order", type=int, choices=(1, 2), default=1)
     ap.add_argument("--optim", choices=("sgd", "adam", "adamax"), default=None)
     ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--batch", type=int, nargs="+", default=None, metavar="B")
     args = ap.parse_args()
     xent, two = args.loss == "xent", args.order == 2
     if xent and two:
@@ -85,6 +130,8 @@ def main():
     nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64).cuda()
     Y = torch.stack([t[0] for _, _, t in graphs]).view(-1, 1).cuda()
     stats = dict(classification=True) if xent else dict(t_mean=MEAN, t_std=STD)
+    if args.batch:
+        return batch_arms(args, nets["torch"], (X, A, nb, Y), stats, optim, nmax)
     steps = {k: CcnTrainStep(nets[k], lr=LR, fused=(k == "fused") and ("ccn2" if two else True), optimizer=optim,
                              momentum=args.momentum, **stats) for k in ("unfused", "fused")}
 
