@@ -373,6 +373,14 @@ CCN_TRAIN_FUSED_OPTIM = {(1, "sgd"): True, (1, "adam"): True, (2, "sgd"): True, 
 # below the pieces route's at both batch sizes; otherwise the pieces route is the default and the kernels stay
 # reachable with fused=True.
 CCN_TRAIN_BATCH_FUSED_DEFAULT = True
+# The same question for CCN_2D and hgnn_ccn2_small_train_batch (fused="ccn2_batch").  Off: fused=None keeps CCN_2D
+# mini-batches on the pieces route, which tests/test_gpu_ccn_train_batch.py pins.  The measured A/B
+# (tools/ab_ccn_train.py --order 2 --batch 32 256, profiles/ccn_train_batch_ab.json, DESIGN.md "CCN-2D mini-batch
+# kernels"), median (min, max) ms per graph of one run: kernels 0.0094 (0.0092, 0.0095) against pieces 0.0115
+# (0.0103, 0.0137) at B = 32, 0.0016 (0.0016, 0.0017) against 0.0018 (0.0018, 0.0019) at B = 256 -- below the pieces
+# at both sizes, by 1.23 and 1.09 times (1.09 and 1.08 in a repeat of the run).  Switching the default is a later
+# change, and one that must also change tests/test_gpu_ccn_train_batch.py.
+CCN2_TRAIN_BATCH_FUSED_DEFAULT = False
 
 
 class CcnTrainStep(_Optimizer):
@@ -432,13 +440,23 @@ class CcnTrainStep(_Optimizer):
       batch_fused  hgnn_ccn_small_train_batch: two dispatches per mini-batch (one workgroup per graph: forward, its
                    dout row, backward; then one wave per parameter element: the sum over the graphs, the gradient, the
                    optimizer update, the meters) -- CCN_1D within hgnn_ccn_small_train_batch_supported, B <= 4096
+      batch_fused2d  hgnn_ccn2_small_train_batch: the same two dispatches for CCN_2D (one workgroup per graph: one
+                   plan, forward, its dout row, backward without dX, in the graph's own workspace region; then the
+                   sums over the mini-batch's nodes and graphs, the gradient, the optimizer update, the meters) --
+                   fused="ccn2_batch", CCN_2D within hgnn_ccn2_small_train_batch_supported (graphs of <= 32 nodes,
+                   input_feats <= 8, hidden_size <= 2, n_outputs <= 256), B <= 4096.  Its workspace holds batch_size
+                   graph regions (about 0.8 MB each at 29 nodes, two layers, hidden 2: about 200 MB at B = 256),
+                   allocated once per nmax and kept
       batch        the library's pieces per mini-batch: forward_batch, hgnn_mse_loss on the device-normalised target
                    with (0, 1) (or hgnn_xent_loss), autograd backward, hgnn_optim_step -- CCN_2D, larger graphs, wider
                    channels.  The same arithmetic bit for bit where both routes exist.
 
     fused=None takes batch_fused where it is supported and CCN_TRAIN_BATCH_FUSED_DEFAULT (the measured default) says
-    so, fused=False never, fused=True raises where it is not supported, fused="ccn2" raises (there is no CCN-2D
-    mini-batch kernel).  Neither route synchronises with the host.  A graph the fused kernels reject (validation
+    so, fused=False never, fused=True raises where it is not supported (so for every CCN_2D model), fused="ccn2" (the
+    per-graph kernel) raises.  fused="ccn2_batch" means the CCN-2D mini-batch kernels: it needs batch_size, raises in
+    the constructor on a model they do not take and in step() on a chunk padded beyond their bound; fused=None keeps
+    CCN_2D on the pieces (CCN2_TRAIN_BATCH_FUSED_DEFAULT, the measured A/B beside it).  No route synchronises with
+    the host.  A graph the fused kernels reject (validation
     bits, or a class target that is no index) makes its whole mini-batch take no step and update no meter; the other
     graphs' out rows are written, the error shows at the next check, and step_count still counts the mini-batch (its
     step number is consumed: the device decides, the host cannot know).
@@ -453,11 +471,20 @@ class CcnTrainStep(_Optimizer):
             raise RuntimeError(f"hgnn_amd: batch_size={batch_size!r}: expected None (the per-graph loop) or an "
                                "integer >= 1")
         if batch_size is not None and isinstance(fused, str) and fused == "ccn2":
-            raise RuntimeError("hgnn_amd: fused=\"ccn2\" with batch_size: there is no CCN-2D mini-batch kernel "
-                               "(fused=None or False runs CCN_2D mini-batches from the library's pieces)")
+            raise RuntimeError("hgnn_amd: fused=\"ccn2\" with batch_size: \"ccn2\" is the per-graph CCN-2D kernel; "
+                               "the CCN-2D mini-batch kernels are fused=\"ccn2_batch\" (fused=None or False runs "
+                               "CCN_2D mini-batches from the library's pieces)")
+        if batch_size is None and isinstance(fused, str) and fused == "ccn2_batch":
+            raise RuntimeError("hgnn_amd: fused=\"ccn2_batch\" needs batch_size (the per-graph CCN-2D kernel is "
+                               "fused=\"ccn2\")")
         self.batch_size = batch_size
         if not isinstance(model, _CCN):
             raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
+        if isinstance(fused, str) and fused == "ccn2_batch":  # a host-only question: asked before the device's
+            cfg = model._spec().config(1, 1)
+            if not L.lib().hgnn_ccn2_small_train_batch_supported(ctypes.byref(cfg)):
+                raise RuntimeError("hgnn_amd: fused=\"ccn2_batch\" needs CCN_2D with input_feats <= 8, hidden_size "
+                                   "<= 2 and n_outputs <= 256 (hgnn_ccn2_small_train_batch_supported)")
         # the reference's rule (train_ccn.py:39): mean == 0 marks generated (classification) data
         if classification is None:
             classification = t_mean is not None and float(t_mean) == 0.0
@@ -486,9 +513,10 @@ class CcnTrainStep(_Optimizer):
         self.spec = model._spec()
         self.fused = fused
         if isinstance(fused, str):
-            if fused != "ccn2":
-                raise RuntimeError(f"hgnn_amd: fused={fused!r}: expected None, False, True or \"ccn2\"")
-            if not self._supported2d(1):
+            if fused not in ("ccn2", "ccn2_batch"):
+                raise RuntimeError(f"hgnn_amd: fused={fused!r}: expected None, False, True, \"ccn2\" or "
+                                   "\"ccn2_batch\"")
+            if fused == "ccn2" and not self._supported2d(1):
                 raise RuntimeError("hgnn_amd: fused=\"ccn2\" needs CCN_2D with input_feats <= 8, hidden_size <= 2 "
                                    "and n_outputs <= 256 (hgnn_ccn2_small_train_supported)")
         elif fused and not self._supported(1):
@@ -496,9 +524,11 @@ class CcnTrainStep(_Optimizer):
                                "(hgnn_ccn_small_train_supported)")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
         self.out = None
-        self.path = None  # "fused", "fused2d" or "unfused" (mini-batch mode: "batch_fused" or "batch"): the last step
+        # "fused", "fused2d" or "unfused" (mini-batch mode: "batch_fused", "batch_fused2d" or "batch"): the last step
+        self.path = None
         self._ws2d = {}   # nmax -> the CCN-2D kernel's one-graph workspace
         self._ws_batch = None  # hgnn_ccn_small_train_batch's workspace (sized once: it does not depend on nmax)
+        self._ws_batch2d = {}  # nmax -> hgnn_ccn2_small_train_batch's workspace (batch_size graph regions)
         self._grads = [torch.zeros_like(p) for p in self.params]
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
         # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
@@ -519,10 +549,12 @@ class CcnTrainStep(_Optimizer):
         cfg = self.spec.config(1, nmax)
         return bool(L.lib().hgnn_ccn2_small_train_supported(ctypes.byref(cfg)))
 
-    def _supported_batch(self, nmax):
-        """Whether hgnn_ccn_small_train_batch takes mini-batches of this step padded to nmax nodes."""
+    def _supported_batch(self, nmax, two=False):
+        """Whether hgnn_ccn_small_train_batch (two: hgnn_ccn2_small_train_batch) takes mini-batches of this step
+        padded to nmax nodes."""
         cfg = self.spec.config(1, nmax)
-        if not L.lib().hgnn_ccn_small_train_batch_supported(ctypes.byref(cfg)):
+        name = "hgnn_ccn2_small_train_batch_supported" if two else "hgnn_ccn_small_train_batch_supported"
+        if not getattr(L.lib(), name)(ctypes.byref(cfg)):
             return False
         # a mini-batch is one call's at most; the entry's MSE meters are hgnn_mse_loss's, which stops dividing
         # below (float)1e-5 where the CCN rule always divides (the entry's own fp32 comparison)
@@ -534,7 +566,15 @@ class CcnTrainStep(_Optimizer):
         """The path of a chunk padded to nmax nodes in mini-batch mode."""
         fused = self.fused
         if fused is None:
-            return "batch_fused" if CCN_TRAIN_BATCH_FUSED_DEFAULT and self._supported_batch(nmax) else "batch"
+            if CCN_TRAIN_BATCH_FUSED_DEFAULT and self._supported_batch(nmax):
+                return "batch_fused"
+            return "batch_fused2d" if CCN2_TRAIN_BATCH_FUSED_DEFAULT and self._supported_batch(nmax, True) else "batch"
+        if fused == "ccn2_batch":
+            if not self._supported_batch(nmax, True):
+                raise RuntimeError(f"hgnn_amd: fused=\"ccn2_batch\", but batch_size = {self.batch_size} at nmax = "
+                                   f"{nmax} is outside the CCN-2D mini-batch kernels' bounds "
+                                   "(hgnn_ccn2_small_train_batch_supported)")
+            return "batch_fused2d"
         if fused:
             if not self._supported_batch(nmax):
                 raise RuntimeError(f"hgnn_amd: fused=True, but batch_size = {self.batch_size} at nmax = {nmax} is "
@@ -595,8 +635,8 @@ class CcnTrainStep(_Optimizer):
         G, nmax = X.shape[0], X.shape[1]
         self.path = path = self._route(nmax)  # before the work: a strict check inside it may raise
         self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
-        if path == "batch_fused":
-            self._step_batch_fused(X, adj, n_batch, y)
+        if path in ("batch_fused", "batch_fused2d"):
+            self._step_batch_fused(X, adj, n_batch, y, two=path == "batch_fused2d")
         elif path == "batch":
             self._step_batch_pieces(X, adj, n_batch, y)
         elif path == "unfused":
@@ -693,9 +733,21 @@ class CcnTrainStep(_Optimizer):
         if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
             self._targets.watch()
 
-    def _step_batch_fused(self, X, adj, n_batch, y):
-        """Mini-batch mode, hgnn_ccn_small_train_batch: one call per run of whole mini-batches within the entry's
-        4096-graph bound."""
+    def _workspace_batch2d(self, nmax, dev):
+        """hgnn_ccn2_small_train_batch's workspace for chunks padded to nmax nodes: batch_size graph regions of about
+        0.8 MB each at nmax = 29, layers = 2, hidden = 2 (so about 200 MB at batch_size = 256), allocated once per
+        nmax and kept, like the per-graph kernel's _ws2d."""
+        ws = self._ws_batch2d.get(nmax)
+        if ws is None:
+            cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, nmax)
+            ws = torch.empty(L.lib().hgnn_ccn2_small_train_batch_workspace_bytes(ctypes.byref(cfg), self.batch_size),
+                             dtype=torch.uint8, device=dev)
+            self._ws_batch2d[nmax] = ws
+        return ws
+
+    def _step_batch_fused(self, X, adj, n_batch, y, two=False):
+        """Mini-batch mode, hgnn_ccn_small_train_batch (two: hgnn_ccn2_small_train_batch): one call per run of whole
+        mini-batches within the entry's 4096-graph bound."""
         from .ccn import _word
         from .net import _capturing, check_errors, strict
         lib = L.lib()
@@ -703,10 +755,16 @@ class CcnTrainStep(_Optimizer):
         dev = X.device
         stream = L.stream_handle(dev)
         B, G = self.batch_size, X.shape[0]
-        if self._ws_batch is None:
-            cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, X.shape[1])
-            self._ws_batch = torch.empty(lib.hgnn_ccn_small_train_batch_workspace_bytes(ctypes.byref(cfg), B),
-                                         dtype=torch.uint8, device=dev)
+        name = "hgnn_ccn2_small_train_batch" if two else "hgnn_ccn_small_train_batch"
+        entry = getattr(lib, name)
+        if two:
+            ws = self._workspace_batch2d(X.shape[1], dev)
+        else:
+            if self._ws_batch is None:
+                cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, X.shape[1])
+                self._ws_batch = torch.empty(lib.hgnn_ccn_small_train_batch_workspace_bytes(ctypes.byref(cfg), B),
+                                             dtype=torch.uint8, device=dev)
+            ws = self._ws_batch
         span = CCN_TRAIN_MAX_GRAPHS // B * B
         s1, s2 = self._states()
         for g0 in range(0, G, span):
@@ -717,12 +775,12 @@ class CcnTrainStep(_Optimizer):
             sc = torch.tensor(self._step_scalars(self.step_count, k),
                               dtype=torch.float32).pin_memory().to(dev, non_blocking=True)
             err, tag = _word.next(dev)
-            L.check(lib.hgnn_ccn_small_train_batch(
+            L.check(entry(
                 ctypes.byref(cfg), B, self._kind, int(self.classification), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]),
                 L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]), self.t_mean, self.t_std,
                 L.ptr_array(self.params), L.ptr_array(self._grads), s1, s2, L.ptr(sc), self._b1(), self.betas[1],
-                self.eps, self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), L.ptr(self._ws_batch), err,
-                tag, stream), "hgnn_ccn_small_train_batch")
+                self.eps, self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), L.ptr(ws), err,
+                tag, stream), name)
             self.step_count += k
         for p, g in zip(self.params, self._grads):
             p.grad = g

@@ -604,7 +604,7 @@ int hgnn_ccn2_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, co
  * optimizer state and the parameters.  (The running loss of the classification branch is formed from the same row
  * losses in the same order.)
  *   supported: host only; 1 for order 1 within hgnn_ccn_small_train_supported's bounds (cfg->bs is not looked at),
- *     else 0 (order 2 has no mini-batch kernel).
+ *     else 0 (order 2: hgnn_ccn2_small_train_batch below).
  *   workspace_bytes: cfg->bs reject words (a call clears and uses the first ceil(bs / batch), one per mini-batch,
  *     with one hipMemsetAsync), then one mini-batch's per-graph regions, each 256-byte aligned: the level partials
  *     [batch][ptot], the readout features [batch][nf] and dout [batch][n_out].  It grows with `batch` and with
@@ -640,6 +640,30 @@ int hgnn_ccn_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, 
                                float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
                                double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
                                int32_t* d_err, int32_t tag, void* stream);
+/* The same for CCN-2D (csrc/ccn2_small_batch.hip): mini-batches of `batch` graphs, one workgroup per graph, two
+ * dispatches per mini-batch ordered by the stream alone.  The first runs plan, forward, the graph's dout row and the
+ * backward (no dX, one plan for both directions) in the graph's own workspace region; the second sums the node
+ * partials and the fc products over the mini-batch in the order of hgnn_ccn_small_backward's batch reduction and
+ * applies the optimizer `kind` to each element.  Bit for bit the pieces on the mini-batch's slice, as above.
+ *   supported: host only; 1 exactly where hgnn_ccn2_small_train_supported is (cfg->bs is not looked at), else 0.
+ *   workspace_bytes: cfg->bs reject words (a call clears and uses the first ceil(bs / batch), one per mini-batch,
+ *     with one hipMemsetAsync), then one mini-batch's regions, each 256-byte aligned and reused by the mini-batches
+ *     of a call in stream order: the readout features [batch][nf], dout [batch][n_out], per level the node partials
+ *     [batch nmax][hidden 18 c_l + hidden], and `batch` graph regions (levels, the dp format, row sums: the
+ *     per-graph region of hgnn_ccn_small_workspace_bytes).  A graph region is about 0.8 MB at nmax = 29,
+ *     layers = 2, hidden = 2, so batch = 256 takes about 200 MB and batch = 4096 about 3.3 GB.  It never shrinks as
+ *     `batch` or cfg->bs grows; nothing in it is read before it is written, apart from the reject words.  0 where
+ *     unsupported, for batch < 1 or bs outside 1 .. 4096.  The caller may keep it across calls on one stream.
+ *   Every argument, d_steps' row rule, d_stats, d_out, empty slots, rejected graphs and the return values: as
+ *     hgnn_ccn_small_train_batch (the refusals are made in the same order, before any pointer is read). */
+int hgnn_ccn2_small_train_batch_supported(const hgnn_ccn_config* cfg);
+size_t hgnn_ccn2_small_train_batch_workspace_bytes(const hgnn_ccn_config* cfg, int batch);
+int hgnn_ccn2_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, int xent, const float* d_X,
+                                const float* d_adj, const int64_t* d_n_batch, const float* d_y, double t_mean,
+                                double t_std, float* const* params, float* const* grads, float* const* state1,
+                                float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
+                                double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
+                                int32_t* d_err, int32_t tag, void* stream);
 /* The evaluation meters of scripts/test_ccn.py:34-67 on the outputs of a forward over n_graphs graphs:
  * d_res[0] = mean over graphs of MSELoss(out_g, y'_g), d_res[1] = mean over graphs of the MAE, y' normalised
  * as above.  One block, fp64 sums in a fixed order: the same bits every call. */

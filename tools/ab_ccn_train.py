@@ -23,8 +23,9 @@ hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt (adamax: the Adamax entries
 profiles/ccn_train_optim_ab.json under the key "order<N>_<loss>_<optim>"; the files above are left alone.
 
 --batch B [B ...] (e.g. --batch 32 256): mini-batch training, CcnTrainStep(batch_size=B), on the same graphs under the
-same protocol -- the per-graph fused loop (order 2: fused2d) against, per B, the pieces route (fused=False) and, for
-order 1, the mini-batch kernels (fused=True: hgnn_ccn_small_train_batch); no torch arm.  Median, min and max ms per
+same protocol -- the per-graph fused loop (order 2: fused2d) against, per B, the pieces route (fused=False) and the
+mini-batch kernels (order 1: fused=True, hgnn_ccn_small_train_batch, arm batch_fused_B<B>; order 2:
+fused="ccn2_batch", hgnn_ccn2_small_train_batch, arm batch_fused2d_B<B>); no torch arm.  Median, min and max ms per
 graph, merged into profiles/ccn_train_batch_ab.json under the key "order<N>_<loss>_<optim>"."""
 import argparse
 import copy
@@ -51,7 +52,9 @@ def batch_arms(args, net, inputs, stats, optim, nmax):
             CcnTrainStep(copy.deepcopy(net), fused="ccn2" if two else True, **kw)}
     for B in args.batch:
         arms[f"batch_pieces_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused=False, batch_size=B, **kw)
-        if not two:  # there is no CCN-2D mini-batch kernel
+        if two:
+            arms[f"batch_fused2d_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused="ccn2_batch", batch_size=B, **kw)
+        else:
             arms[f"batch_fused_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused=True, batch_size=B, **kw)
     G = inputs[0].shape[0]
     times = {k: [] for k in arms}
