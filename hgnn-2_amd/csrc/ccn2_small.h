@@ -1,7 +1,15 @@
 // Device and host helpers of the CCN-2D small-graph kernels, shared by ccn2_small.hip (the one-shot forward and
-// backward) and ccn2_small_train.hip (the per-graph training loop): the LDS layout, the plan, one node of a
-// forward / backward level, the gather, the readout sums and the workspace layout.  Two translation units, so
-// that the training kernel's extra callers leave the one-shot kernels' inlining, and with it their code, alone.
+// backward), ccn2_small_train.hip (the per-graph training loop) and ccn2_small_batch.hip (the mini-batch kernels).
+//   * the LDS layout (QGraph, QWave, q_carve), the graph region (q_region) and the plan (q_plan);
+//   * one node of a level: q_node_fwd, q_node_bwd, q_node_gather, q_node_dx0;
+//   * the stages the kernels are lists of, each defined once: q_forward, q_readout, q_dsum, q_fc_grads, q_backward,
+//     and the two per-element sums over a mini-batch, q_sum_level_elem / q_sum_fc_elem.  A stage inlines its node
+//     functions ([[clang::always_inline]]): the training kernels instantiate each twice, and an outlined node
+//     function would spill the wave's state around every call;
+//   * the host side: the workspace layout (q_layout), QArgs from a config (q_args, q_set_grads) and the LDS opt-in.
+// Every stage carries a bitwise contract (its order of summation is that of k_ccn_readout, k_ccn_param_reduce or
+// k_ccn_readout_bwd), which is why there is one definition.  The units stay separate translation units, so that one
+// kernel's callers leave the others' inlining, and with it their code, alone.
 #pragma once
 #include <cstdint>
 
@@ -18,6 +26,10 @@ constexpr int Q_HC = 2;
 constexpr int Q_LMAX = 15;
 constexpr int Q_NF = 64;                     // readout width bound (f + L h <= 8 + 15 * 2)
 constexpr int Q_RT = 256;                    // threads of the general readout / reduction kernels
+// the training kernels (ccn2_small_train.hip, ccn2_small_batch.hip)
+constexpr int Q_TMAX = 2 * Q_LMAX + 2;       // parameter tensors: level weights and biases, fc weight and bias
+constexpr int Q_TRAIN_GMAX = 4096;           // graphs per call
+constexpr int Q_OMAX = 256;                  // n_out bound: the graph's out / dout row in static LDS
 
 struct QArgs {
     const float* adj;          // (bs, nmax, nmax) with self loops
@@ -821,6 +833,264 @@ __device__ void q_node_gather(const QArgs& a, QGraph& g, QWave& w, short* sp, in
     wsync();
 }
 
+// dX[j] = sum over neighbours i of G_i[a_j] + d_j^2 dsum0 (k_ccn2_dx0), g0 being level 0's per-neighbour terms
+__device__ void q_node_dx0(const QArgs& a, const QGraph& g, int b, int j, const float* g0, int cin) {
+    const int lane = threadIdx.x & 63;
+    const int nj = g.deg[j];
+    float t[Q_CF];
+#pragma unroll
+    for (int c = 0; c < Q_CF; ++c) t[c] = 0.f;
+    for (int x = lane; x < nj; x += 64) {
+        const int i = g.nbr[j * Q_N + x];
+        const unsigned long long mi = g.bits[i];
+        const int aj = __popcll(mi & ((1ull << j) - 1ull));  // position of j in N(i)
+        const float* gi = g0 + ((long long)g.off1[i] + aj) * cin;
+#pragma unroll
+        for (int c = 0; c < Q_CF; ++c)
+            if (c < cin) t[c] += gi[c];
+    }
+#pragma unroll
+    for (int c = 0; c < Q_CF; ++c) {
+        if (c >= cin) break;
+        const float s = wave_sum(t[c]);
+        if (lane == 0) {
+            const float rd = g.vec[c];
+            a.dX[((long long)b * a.nmax + j) * a.f + c] = s + (float)(nj * nj) * rd;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the stages of a kernel
+// The block's graph state, this wave's state and its two scratch arrays (sp: the position maps; P: the forward's
+// P, the backward's dp) in the dynamic LDS
+struct QLds {
+    QGraph& g;
+    QWave& w;
+    short* sp;
+    float* P;
+};
+__device__ __forceinline__ QLds q_carve(char* lds, const QArgs& a) {
+    char* wbase = lds + q_al16(sizeof(QGraph)) + (size_t)(threadIdx.x >> 6) * q_wave_bytes(a.nmax);
+    return {*reinterpret_cast<QGraph*>(lds), *reinterpret_cast<QWave*>(wbase),
+            reinterpret_cast<short*>(wbase + q_al16(sizeof(QWave))),
+            reinterpret_cast<float*>(wbase + q_al16(sizeof(QWave)) + q_sp_bytes(a.nmax))};
+}
+
+// What a graph region G holds behind its L levels: the two dF buffers, dp's row sums and traces, level 0's terms
+struct QRegion {
+    float *dA, *dB, *rdp, *trd, *g0;
+};
+__device__ __forceinline__ QRegion q_region(const QArgs& a, float* G) {
+    QRegion r;
+    r.dA = G + (long long)a.L * a.r2 * a.h;
+    r.dB = r.dA + a.r2 * a.h;
+    r.rdp = r.dB + a.r2 * a.h;
+    r.trd = r.rdp + a.r1 * a.h;
+    r.g0 = r.trd + (long long)a.nmax * a.h;
+    return r;
+}
+
+// the lanes' validation bits into the block's word
+__device__ __forceinline__ void q_report(uint32_t bad, uint32_t& sbad) {
+    for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
+    if ((threadIdx.x & 63) == 0 && bad) atomicOr(&sbad, bad);
+}
+
+// Forward: the readout's level-0 column sum, then per level the combined weights, the node pass into the level's
+// rows of the graph region G and the column sum of the nodes' sums.  Leaves the readout features in g.vec.
+// FR (here and below): parameters are read by agent-scope loads (c2_ld; the per-graph training loop).
+template <int CF, bool FR>
+__device__ __forceinline__ void q_forward(const QArgs& a, QGraph& g, QWave& w, short* sp, float* P, int n, float* G) {
+    const int wv = threadIdx.x >> 6;
+    const int f = a.f, h = a.h;
+    // level 0 of the readout: sum_i d_i^2 X[i] (utils_ccn.py:167-172 tile X[i] d_i x d_i times)
+    [[clang::always_inline]] q_colsum(g, n, f, 0, [&](int r, int c, double& acc) {
+        const double d = g.deg[r];
+        const double wgt = d * d;
+        acc += wgt * (double)g.Xs[r * f + c];
+    });
+    for (int l = 0; l < a.L; ++l) {
+        const int cin = l == 0 ? f : h;
+        float* fout = G + (long long)l * a.r2 * h;
+        const float* fin = l == 0 ? nullptr : G + (long long)(l - 1) * a.r2 * h;
+        if (l == 0) c2_weights<Q_HC, CF, FR>(reinterpret_cast<float(*)[Q_HC][CF]>(g.wc), a.W[l], cin, 0, h);
+        else c2_weights<Q_HC, Q_HC, FR>(reinterpret_cast<float(*)[Q_HC][Q_HC]>(g.wc), a.W[l], cin, 0, h);
+        __syncthreads();
+        for (int i = wv; i < n; i += Q_NW) {
+            if (l == 0) [[clang::always_inline]] q_node_fwd<CF, 1, true, FR>(a, g, w, sp, P, i, l, fin, cin, fout);
+            else [[clang::always_inline]] q_node_fwd<Q_HC, 8, false, FR>(a, g, w, sp, P, i, l, fin, cin, fout);
+        }
+        __syncthreads();
+        [[clang::always_inline]] q_colsum(g, n, h, f + l * h,
+                                          [&](int r, int c, double& acc) { acc += (double)g.nsum[l][r][c]; });
+    }
+}
+
+// out = fc(feat) in fp64 (k_ccn_readout's order) from the features in g.vec: out_row[o], and keep[o] when the
+// kernel goes on with the row (keep: LDS, read after the caller's next barrier).  sred: 4 doubles of LDS.
+template <bool FR>
+__device__ __forceinline__ void q_readout(const QArgs& a, const QGraph& g, int nf, double* sred, float* out_row,
+                                          float* keep) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int o = 0; o < a.n_out; ++o) {
+        double s = 0.0;
+        if ((int)threadIdx.x < Q_RT)
+            for (int k = threadIdx.x; k < nf; k += Q_RT) s += (double)c2_ld<FR>(a.fcw + o * nf + k) * (double)g.vec[k];
+        s = wave_sum_d(s);
+        __syncthreads();
+        if (lane == 0 && wv < 4) sred[wv] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const double t = sred[0] + sred[1] + sred[2] + sred[3];
+            const float ov = (float)(t + (double)c2_ld<FR>(a.fcb + o));
+            out_row[o] = ov;
+            if (keep) keep[o] = ov;
+        }
+    }
+}
+
+// dsum[k] = sum_o dout[o] fcw[o][k] (k_ccn_readout_bwd's order) into g.vec, dob being the graph's dout row
+template <bool FR>
+__device__ __forceinline__ void q_dsum(const QArgs& a, QGraph& g, const float* dob, int nf) {
+    for (int k = threadIdx.x; k < nf; k += Q_NT) {
+        float s = 0.f;
+        for (int o = 0; o < a.n_out; ++o) s = fmaf(dob[o], c2_ld<FR>(a.fcw + o * nf + k), s);
+        g.vec[k] = s;
+    }
+}
+
+// The fc gradients of one graph (the one-graph layout): k_ccn_readout_bwd's wave per output; feat: the graph's
+// readout features, its workspace row or g.vec before q_dsum takes it
+__device__ __forceinline__ void q_fc_grads(const QArgs& a, const float* dob, const float* feat, int nf) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int q = wv; q < a.n_out * nf + a.n_out; q += Q_NW) {
+        double s = 0.0;
+        if (q < a.n_out * nf) {
+            const int o = q / nf, k = q % nf;
+            if (lane < 1) s += (double)dob[o] * (double)feat[k];
+        } else if (lane < 1) {
+            s += (double)dob[q - a.n_out * nf];
+        }
+        s = wave_sum_d(s);
+        if (lane == 0) {
+            if (q < a.n_out * nf) a.gfcw[q] = (float)s;
+            else a.gfcb[q - a.n_out * nf] = (float)s;
+        }
+    }
+}
+
+// Backward level walk on the plan and the levels of the forward, dsum in g.vec: per level the combined weights, the
+// node pass (dp format, the node's parameter partials at its packed index), then the gather of dF_{l-1} (the
+// combined weights in g.wc are this level's: c2_dT_weights' values) and the swap of the two dF buffers.
+// reduce (block-uniform; the one-graph layout): the parameter gradients are summed here, in k_ccn_param_reduce's
+// order over the graph's nodes.  DX: level 0 also forms its per-neighbour terms and dX (graph b's rows).
+// k_ccn2_small_train (ccn2_small_train.hip) carries a written-out copy of this walk (FR, no DX, reduce), kept for a
+// measured 0.8 % of its time; a change here goes there too.
+template <int CF, bool FR, bool DX>
+__device__ __forceinline__ void q_backward(const QArgs& a, QGraph& g, QWave& w, short* sp, float* dpL, int b, int n,
+                                           float* G, const QRegion& r, bool reduce) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int f = a.f, h = a.h, L = a.L;
+    float* dcur = r.dA;
+    float* dnext = r.dB;
+    for (int l = L - 1; l >= 0; --l) {
+        const int cin = l == 0 ? f : h;
+        const int K = 18 * cin, stride = h * K + h;
+        float* pl = a.ppart[l];
+        const float* Fl = G + (long long)l * a.r2 * h;
+        const float* fin = l == 0 ? nullptr : G + (long long)(l - 1) * a.r2 * h;
+        const float* dtop = l == L - 1 ? g.vec + f + (L - 1) * h : nullptr;
+        if (l == 0) c2_weights<Q_HC, CF, FR>(reinterpret_cast<float(*)[Q_HC][CF]>(g.wc), a.W[l], cin, 0, h);
+        else c2_weights<Q_HC, Q_HC, FR>(reinterpret_cast<float(*)[Q_HC][Q_HC]>(g.wc), a.W[l], cin, 0, h);
+        __syncthreads();
+        for (int i = wv; i < n; i += Q_NW) {
+            float* pp = pl + (long long)(g.base + i) * stride;
+            if (l == 0)
+                [[clang::always_inline]] q_node_bwd<CF, 1, true, DX>(a, g, w, sp, dpL, i, dcur, dtop, Fl, fin, cin,
+                                                                     r.rdp, r.trd, pp, DX ? r.g0 : nullptr);
+            else
+                [[clang::always_inline]] q_node_bwd<Q_HC, 8, false>(a, g, w, sp, dpL, i, dcur, dtop, Fl, fin, cin,
+                                                                    r.rdp, r.trd, pp, nullptr);
+        }
+        __syncthreads();
+        if (reduce)
+            for (int k = wv; k < stride; k += Q_NW) {
+                double s = 0.0;
+                if (lane < n) s += (double)pl[(long long)lane * stride + k];
+                s = wave_sum_d(s);
+                if (lane == 0) {
+                    const double z = 0.0, t = ((s + z) + z) + z;
+                    if (k < h * K) a.gW[l][k] = (float)t;
+                    else a.gB[l][k - h * K] = (float)t;
+                }
+            }
+        if (l > 0) {
+            for (int j = wv; j < n; j += Q_NW)
+                [[clang::always_inline]] q_node_gather(a, g, w, sp, j, dcur, r.rdp, r.trd, g.vec + f + (l - 1) * h,
+                                                       dnext);
+        } else if constexpr (DX) {
+            for (int j = wv; j < n; j += Q_NW) [[clang::always_inline]] q_node_dx0(a, g, b, j, r.g0, cin);
+        }
+        __syncthreads();
+        float* t = dcur;
+        dcur = dnext;
+        dnext = t;
+    }
+}
+
+// ---------------------------------------------------------------- per-element sums over a mini-batch of B graphs
+// (256-thread blocks; QArgs' n_batch, ppart and feat are the mini-batch's)
+// Block index k < np -> level l and its element k of the level's [h K_l + h] partial row; K = K_l
+__device__ __forceinline__ void q_level_elem(const QArgs& a, int& k, int& l, int& K) {
+    for (l = 0; l < a.L; ++l) {
+        const int st = a.h * 18 * (l == 0 ? a.f : a.h) + a.h;
+        if (k < st) break;
+        k -= st;
+    }
+    K = 18 * (l == 0 ? a.f : a.h);
+}
+
+// Element k of level l's parameter gradient: the sum over the mini-batch's packed nodes in k_ccn_param_reduce's
+// order, valid on thread 0.  red: 4 doubles, s_tot: an int of LDS.
+__device__ __forceinline__ double q_sum_level_elem(const QArgs& a, int B, int l, int k, int stride, double* red,
+                                                   int& s_tot) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x < 64) {  // total nodes of the mini-batch (the packed index range)
+        int s = 0;
+        for (int q = lane; q < B; q += 64) {
+            const long long v = a.n_batch ? a.n_batch[q] : a.nmax;
+            s += v < 0 ? 0 : (v > a.nmax ? a.nmax : (int)v);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) s_tot = s;
+    }
+    __syncthreads();
+    const int n = s_tot;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += (double)a.ppart[l][(long long)i * stride + k];
+    s = wave_sum_d(s);
+    if (lane == 0) red[wv] = s;
+    __syncthreads();
+    return threadIdx.x == 0 ? red[0] + red[1] + red[2] + red[3] : 0.0;
+}
+
+// Element e of the fc gradient ([n_out][nf] weights, then n_out biases): this wave's sum over the mini-batch's
+// graphs in k_ccn_readout_bwd's order, valid on lane 0.  dout: [B][n_out]
+__device__ __forceinline__ double q_sum_fc_elem(const QArgs& a, const float* dout, int B, int e, int nf) {
+    const int lane = threadIdx.x & 63;
+    double s = 0.0;
+    if (e < a.n_out * nf) {
+        const int o = e / nf, k = e % nf;
+        for (int b = lane; b < B; b += 64) s += (double)dout[b * a.n_out + o] * (double)a.feat[(long long)b * nf + k];
+    } else {
+        const int o = e - a.n_out * nf;
+        for (int b = lane; b < B; b += 64) s += (double)dout[b * a.n_out + o];
+    }
+    return wave_sum_d(s);
+}
+
+// ---------------------------------------------------------------- host
 int q_nf(const hgnn_ccn_config* c) { return c->f_in + c->layers * c->hidden; }
 long long q_prow(const hgnn_ccn_config* c, int l) {
     const int K = 18 * (l == 0 ? c->f_in : c->hidden);
@@ -833,10 +1103,37 @@ long long q_gstride(const hgnn_ccn_config* c) {
     return (fl + 63) / 64 * 64;
 }
 size_t q_al256(size_t x) { return (x + 255) / 256 * 256; }
+// grids of the per-element sums: one block per level-parameter element, one wave of a 256-thread block per fc element
+int q_np(const hgnn_ccn_config* c) {
+    int np = 0;
+    for (int l = 0; l < c->layers; ++l) np += (int)q_prow(c, l);
+    return np;
+}
+int q_nfc(const hgnn_ccn_config* c) { return (c->n_out * q_nf(c) + c->n_out + 3) / 4; }
 
-// workspace: feat, the per-level partial rows, the graph regions
+// Workspace of `graphs` graphs in parallel, byte offsets from `base`: feat [graphs][nf], `extra_bytes` of the
+// caller's, per level ppart [graphs nmax][prow_l], then the graph regions of q_gstride floats (a multiple of 256
+// bytes); every region 256-byte aligned
+struct QLayout {
+    size_t feat, extra, ppart[Q_LMAX], gws, total;
+};
+QLayout q_layout(const hgnn_ccn_config* c, int graphs, size_t base = 0, size_t extra_bytes = 0) {
+    QLayout w{};
+    w.feat = base;
+    w.extra = w.feat + q_al256(4 * (size_t)graphs * q_nf(c));
+    size_t p = w.extra + q_al256(extra_bytes);
+    for (int l = 0; l < c->layers; ++l) {
+        w.ppart[l] = p;
+        p += q_al256(4 * (size_t)graphs * c->nmax * q_prow(c, l));
+    }
+    w.gws = p;
+    w.total = p + 4 * (size_t)graphs * q_gstride(c);
+    return w;
+}
+
+// QArgs of a config (bs graphs in parallel) on a workspace laid out by `lay`
 QArgs q_args(const hgnn_ccn_config* c, const float* X, const float* adj, const int64_t* nb, const float* const* params,
-             void* ws) {
+             void* ws, const QLayout& lay) {
     QArgs a{};
     a.adj = adj;
     a.n_batch = nb;
@@ -857,21 +1154,27 @@ QArgs q_args(const hgnn_ccn_config* c, const float* X, const float* adj, const i
     a.fcw = params[2 * c->layers];
     a.fcb = params[2 * c->layers + 1];
     char* p = static_cast<char*>(ws);
-    a.feat = reinterpret_cast<float*>(p);
-    p += q_al256(4 * (size_t)c->bs * q_nf(c));
-    for (int l = 0; l < c->layers; ++l) {
-        a.ppart[l] = reinterpret_cast<float*>(p);
-        p += q_al256(4 * (size_t)c->bs * c->nmax * q_prow(c, l));
-    }
-    a.gws = reinterpret_cast<float*>(p);
+    a.feat = reinterpret_cast<float*>(p + lay.feat);
+    for (int l = 0; l < c->layers; ++l) a.ppart[l] = reinterpret_cast<float*>(p + lay.ppart[l]);
+    a.gws = reinterpret_cast<float*>(p + lay.gws);
     return a;
 }
 
+void q_set_grads(QArgs& a, float* const* grads, int L) {
+    for (int l = 0; l < L; ++l) {
+        a.gW[l] = grads[2 * l];
+        a.gB[l] = grads[2 * l + 1];
+    }
+    a.gfcw = grads[2 * L];
+    a.gfcb = grads[2 * L + 1];
+}
+
+// the dynamic-LDS opt-in of a kernel, once; static_bytes: the kernel's static LDS, which counts against the same cap
 template <typename K>
-void q_lds_attr(K kernel, bool& done) {
+void q_lds_attr(K kernel, bool& done, size_t static_bytes = 0) {
     if (!done) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)Q_LDS_MAX);
+                                  (int)(Q_LDS_MAX - static_bytes));
         (void)hipGetLastError();  // a refused opt-in shows at the launch, not here
         done = true;
     }

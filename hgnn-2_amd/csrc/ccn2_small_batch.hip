@@ -16,17 +16,15 @@
 // A graph with validation bits (or a class target that is no index) ORs them into the mini-batch's reject word;
 // the apply kernel reads that word first and does nothing when it is set.
 // The arithmetic is that of the library's own pieces on the mini-batch -- hgnn_ccn_small_forward, hgnn_mse_loss /
-// hgnn_xent_loss, hgnn_ccn_small_backward, hgnn_optim_step -- bit for bit: the node functions are shared
-// (ccn2_small.h, kernels.h) and the sums run in the same order.
+// hgnn_xent_loss, hgnn_ccn_small_backward, hgnn_optim_step -- bit for bit: the stages and the per-element sums are
+// the one-shot kernels' own (ccn2_small.h: q_forward, q_readout, q_dsum, q_backward, q_sum_level_elem,
+// q_sum_fc_elem), the loss rows and optimizer elements are kernels.h's.
 #include "ccn2_small.h"
 
 namespace hgnn {
 namespace {
 
-constexpr int QB_TMAX = 2 * Q_LMAX + 2;  // parameter tensors: level weights and biases, fc weight and bias
-constexpr int QB_GMAX = 4096;            // graphs per call (k_ccn2_small_train's bound)
-constexpr int QB_OMAX = 256;             // n_out bound of hgnn_ccn2_small_train_supported: the out / dout row
-constexpr size_t QB_STATIC = 4 * QB_OMAX + 8 * 4 + 64;  // sout, sred, sbad and alignment slack
+constexpr size_t QB_STATIC = 4 * Q_OMAX + 8 * 4 + 64;  // sout, sred, sbad and alignment slack
 
 // One mini-batch: what both kernels need besides QArgs (whose X / adj / n_batch / out point at the mini-batch's
 // first graph and whose bs is the mini-batch's size; feat / ppart / gws are the workspace regions).
@@ -41,77 +39,33 @@ struct QbBatch {
 struct QbApply {
     const float* steps;  // the mini-batch's two per-step scalars (hgnn_ccn2_small_train_opt's row)
     OptScalars h;
-    float* p[QB_TMAX];
-    float* m[QB_TMAX];
-    float* u[QB_TMAX];   // SGD: not touched
+    float* p[Q_TMAX];
+    float* m[Q_TMAX];
+    float* u[Q_TMAX];    // SGD: not touched
     float* stats;        // [4] loss, mae and their RunningAverages
 };
 
-// The node functions are inlined at each call, as in k_ccn2_small_train: two instantiations call each of them, and
-// an outlined node function would spill the wave's state around every call.
+// Stages 1, 2 and 4 are the shared stage functions of ccn2_small.h (FR = false: plain parameter loads); the dout
+// row (3) is this kernel's own.
 template <int CF, bool XENT>
 __global__ void __launch_bounds__(Q_NT) k_ccn2_small_batch(QArgs a, QbBatch t) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
     __shared__ double sred[4];
-    __shared__ float sout[QB_OMAX];  // out[b], then dout[b]
-    QGraph& g = *reinterpret_cast<QGraph*>(lds);
+    __shared__ float sout[Q_OMAX];  // out[b], then dout[b]
+    auto [g, w, sp, P] = q_carve(lds, a);  // P: forward P, backward dp
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    char* wbase = lds + q_al16(sizeof(QGraph)) + (size_t)wv * q_wave_bytes(a.nmax);
-    QWave& w = *reinterpret_cast<QWave*>(wbase);
-    short* sp = reinterpret_cast<short*>(wbase + q_al16(sizeof(QWave)));
-    float* P = reinterpret_cast<float*>(wbase + q_al16(sizeof(QWave)) + q_sp_bytes(a.nmax));  // forward P, backward dp
-    const int f = a.f, h = a.h, L = a.L, nf = f + L * h, n_out = a.n_out;
+    const int nf = a.f + a.L * a.h, n_out = a.n_out;
     float* G = a.gws + (long long)b * a.gstride;  // the graph's own region
-    float* dA = G + (long long)L * a.r2 * h;
-    float* dB = dA + a.r2 * h;
-    float* rdp = dB + a.r2 * h;
-    float* trd = rdp + a.r1 * h;
     // 1. plan; the validation bits into the block's word
     if (threadIdx.x == 0) sbad = 0;
     uint32_t bad = 0;
     const int n = q_nodes(a, b, bad);
     [[clang::always_inline]] bad |= q_plan<false>(a, b, n, g);
-    for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
-    if (lane == 0 && bad) atomicOr(&sbad, bad);
-    // 2. forward: k_ccn2_small_fwd's body, every level kept in the graph's region
-    [[clang::always_inline]] q_colsum(g, n, f, 0, [&](int r, int c, double& acc) {
-        const double d = g.deg[r];
-        const double wgt = d * d;
-        acc += wgt * (double)g.Xs[r * f + c];
-    });
-    for (int l = 0; l < L; ++l) {
-        const int cin = l == 0 ? f : h;
-        float* fout = G + (long long)l * a.r2 * h;
-        const float* fin = l == 0 ? nullptr : G + (long long)(l - 1) * a.r2 * h;
-        if (l == 0) c2_weights<Q_HC, CF>(reinterpret_cast<float(*)[Q_HC][CF]>(g.wc), a.W[l], cin, 0, h);
-        else c2_weights<Q_HC, Q_HC>(reinterpret_cast<float(*)[Q_HC][Q_HC]>(g.wc), a.W[l], cin, 0, h);
-        __syncthreads();
-        for (int i = wv; i < n; i += Q_NW) {
-            if (l == 0) [[clang::always_inline]] q_node_fwd<CF, 1, true, false>(a, g, w, sp, P, i, l, fin, cin, fout);
-            else [[clang::always_inline]] q_node_fwd<Q_HC, 8, false, false>(a, g, w, sp, P, i, l, fin, cin, fout);
-        }
-        __syncthreads();
-        [[clang::always_inline]] q_colsum(g, n, h, f + l * h,
-                                          [&](int r, int c, double& acc) { acc += (double)g.nsum[l][r][c]; });
-    }
-    // out = fc(feat) in fp64 (k_ccn_readout's order); the readout features stay in g.vec
-    for (int o = 0; o < n_out; ++o) {
-        double s = 0.0;
-        if ((int)threadIdx.x < Q_RT)
-            for (int k = threadIdx.x; k < nf; k += Q_RT) s += (double)a.fcw[o * nf + k] * (double)g.vec[k];
-        s = wave_sum_d(s);
-        __syncthreads();
-        if (lane == 0 && wv < 4) sred[wv] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const double tt = sred[0] + sred[1] + sred[2] + sred[3];
-            const float ov = (float)(tt + (double)a.fcb[o]);
-            a.out[(long long)b * n_out + o] = ov;
-            sout[o] = ov;
-        }
-    }
+    q_report(bad, sbad);
+    // 2. forward, every level kept in the graph's region; out[b]; the readout features stay in g.vec
+    q_forward<CF, false>(a, g, w, sp, P, n, G);
+    q_readout<false>(a, g, nf, sred, a.out + (long long)b * n_out, sout);
     // a target that is no class index rejects the graph like a validation bit: set before the barrier the read
     // of sbad follows, so the branch below is block-uniform
     int ti = 0;
@@ -147,45 +101,12 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_batch(QArgs a, QbBatch t) {
     for (int k = threadIdx.x; k < nf; k += Q_NT) a.feat[(long long)b * nf + k] = g.vec[k];
     for (int i = threadIdx.x; i < n_out; i += Q_NT) t.dout[(long long)b * n_out + i] = dob[i];
     __syncthreads();
-    // 4. backward, k_ccn2_small_bwd's batch form on the plan and levels of the forward: dsum, then per level the node
-    // pass (partials at the packed node index) and the gather.  No dX: the level-0 terms that feed only dX and its
-    // sum are left out (q_node_bwd<.., DX = false>); no parameter reduction: the apply kernel sums over the nodes.
-    for (int k = threadIdx.x; k < nf; k += Q_NT) {
-        float s = 0.f;
-        for (int o = 0; o < n_out; ++o) s = fmaf(dob[o], a.fcw[o * nf + k], s);
-        g.vec[k] = s;
-    }
+    // 4. backward, the batch form on the plan and levels of the forward: dsum, then the level walk (partials at the
+    // packed node index).  No dX: the level-0 terms that feed only dX and its sum are left out (DX = false); no
+    // parameter reduction: the apply kernel sums over the nodes.
+    q_dsum<false>(a, g, dob, nf);
     __syncthreads();
-    float* dcur = dA;
-    float* dnext = dB;
-    for (int l = L - 1; l >= 0; --l) {
-        const int cin = l == 0 ? f : h;
-        const int K = 18 * cin, stride = h * K + h;
-        float* pl = a.ppart[l];
-        const float* Fl = G + (long long)l * a.r2 * h;
-        const float* fin = l == 0 ? nullptr : G + (long long)(l - 1) * a.r2 * h;
-        const float* dtop = l == L - 1 ? g.vec + f + (L - 1) * h : nullptr;
-        if (l == 0) c2_weights<Q_HC, CF>(reinterpret_cast<float(*)[Q_HC][CF]>(g.wc), a.W[l], cin, 0, h);
-        else c2_weights<Q_HC, Q_HC>(reinterpret_cast<float(*)[Q_HC][Q_HC]>(g.wc), a.W[l], cin, 0, h);
-        __syncthreads();
-        for (int i = wv; i < n; i += Q_NW) {
-            float* pp = pl + (long long)(g.base + i) * stride;
-            if (l == 0)
-                [[clang::always_inline]] q_node_bwd<CF, 1, true, false>(a, g, w, sp, P, i, dcur, dtop, Fl, fin, cin, rdp,
-                                                                        trd, pp, nullptr);
-            else
-                [[clang::always_inline]] q_node_bwd<Q_HC, 8, false>(a, g, w, sp, P, i, dcur, dtop, Fl, fin, cin, rdp, trd,
-                                                                    pp, nullptr);
-        }
-        __syncthreads();
-        if (l > 0)
-            for (int j = wv; j < n; j += Q_NW)
-                [[clang::always_inline]] q_node_gather(a, g, w, sp, j, dcur, rdp, trd, g.vec + f + (l - 1) * h, dnext);
-        __syncthreads();
-        float* x = dcur;
-        dcur = dnext;
-        dnext = x;
-    }
+    q_backward<CF, false, false>(a, g, w, sp, P, b, n, G, q_region(a, G), false);
 }
 
 // k_ccn2_small_reduce's sums over one mini-batch, each followed by the optimizer's update of its element.  Blocks
@@ -198,42 +119,20 @@ __global__ void __launch_bounds__(256) k_ccn2_small_apply(QArgs a, QbBatch t, Qb
     __shared__ double red[4];
     __shared__ int s_tot;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int h = a.h, f = a.f, L = a.L, nf = f + L * h, n_out = a.n_out, B = t.B;
+    const int L = a.L, nf = a.f + L * a.h, n_out = a.n_out, B = t.B;
     float c1 = 0.f;
     if constexpr (OPT == HGNN_OPT_ADAM) c1 = q.steps[1];
     if ((int)blockIdx.x < np) {
-        int k = blockIdx.x, l = 0;
-        for (; l < L; ++l) {
-            const int K = 18 * (l == 0 ? f : h), st = h * K + h;
-            if (k < st) break;
-            k -= st;
-        }
-        const int K = 18 * (l == 0 ? f : h), stride = h * K + h;
-        if (threadIdx.x < 64) {  // total nodes of the mini-batch (the packed index range)
-            int s = 0;
-            for (int i = lane; i < B; i += 64) {
-                const long long v = a.n_batch ? a.n_batch[i] : a.nmax;
-                s += v < 0 ? 0 : (v > a.nmax ? a.nmax : (int)v);
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            if (lane == 0) s_tot = s;
-        }
-        __syncthreads();
-        const int n = s_tot;
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n; i += 256) s += (double)a.ppart[l][(long long)i * stride + k];
-        s = wave_sum_d(s);
-        if (lane == 0) red[wv] = s;
-        __syncthreads();
+        int k = blockIdx.x, l, K;
+        q_level_elem(a, k, l, K);
+        const double tt = q_sum_level_elem(a, B, l, k, a.h * K + a.h, red, s_tot);
         if (threadIdx.x == 0) {
-            const double tt = red[0] + red[1] + red[2] + red[3];
             const float gv = (float)tt;
-            if (k < h * K) {
+            if (k < a.h * K) {
                 a.gW[l][k] = gv;
                 optim_at<OPT>(q.p[2 * l], gv, q.m[2 * l], q.u[2 * l], k, q.steps[0], c1, q.h);
             } else {
-                const int e = k - h * K;
+                const int e = k - a.h * K;
                 a.gB[l][e] = gv;
                 optim_at<OPT>(q.p[2 * l + 1], gv, q.m[2 * l + 1], q.u[2 * l + 1], e, q.steps[0], c1, q.h);
             }
@@ -243,15 +142,7 @@ __global__ void __launch_bounds__(256) k_ccn2_small_apply(QArgs a, QbBatch t, Qb
     if ((int)blockIdx.x < np + nfc) {
         const int e = ((int)blockIdx.x - np) * 4 + wv;
         if (e >= n_out * nf + n_out) return;
-        double s = 0.0;
-        if (e < n_out * nf) {
-            const int o = e / nf, k = e % nf;
-            for (int b = lane; b < B; b += 64) s += (double)t.dout[b * n_out + o] * (double)a.feat[(long long)b * nf + k];
-        } else {
-            const int o = e - n_out * nf;
-            for (int b = lane; b < B; b += 64) s += (double)t.dout[b * n_out + o];
-        }
-        s = wave_sum_d(s);
+        const double s = q_sum_fc_elem(a, t.dout, B, e, nf);
         if (lane != 0) return;
         const float gv = (float)s;
         if (e < n_out * nf) {
@@ -298,22 +189,8 @@ __global__ void __launch_bounds__(256) k_ccn2_small_apply(QArgs a, QbBatch t, Qb
 // workspace sized for (bs, batch) serves every call with no more graphs and no larger mini-batches; a call uses and
 // clears the first ceil(bs / batch)), then one mini-batch's regions, each 256-byte aligned and reused by successive
 // mini-batches: feat [B][nf], dout [B][n_out], per level ppart [B nmax][prow_l], B graph regions of q_gstride floats.
-struct QbLayout {
-    size_t feat, dout, ppart[Q_LMAX], gws, total;  // byte offsets
-};
-
-QbLayout qb_layout(const hgnn_ccn_config* c, int batch) {
-    QbLayout w;
-    w.feat = q_al256(4 * (size_t)c->bs);
-    w.dout = w.feat + q_al256(4 * (size_t)batch * q_nf(c));
-    size_t p = w.dout + q_al256(4 * (size_t)batch * c->n_out);
-    for (int l = 0; l < c->layers; ++l) {
-        w.ppart[l] = p;
-        p += q_al256(4 * (size_t)batch * c->nmax * q_prow(c, l));
-    }
-    w.gws = p;
-    w.total = p + q_al256(4 * (size_t)batch * q_gstride(c));
-    return w;
+QLayout qb_layout(const hgnn_ccn_config* c, int batch) {
+    return q_layout(c, batch, q_al256(4 * (size_t)c->bs), 4 * (size_t)batch * c->n_out);  // .extra: dout
 }
 
 template <bool XENT, int OPT>
@@ -327,26 +204,17 @@ int qb_train(const hgnn_ccn_config* cfg, int batch, const float* d_X, const floa
     if (TWO && !state2) return HGNN_ERR_ARG;
     for (int k = 0; k < nt; ++k)
         if (!params[k] || !grads[k] || !state1[k] || (TWO && !state2[k])) return HGNN_ERR_ARG;
-    const QbLayout lay = qb_layout(cfg, batch);
+    const QLayout lay = qb_layout(cfg, batch);
     char* ws = static_cast<char*>(workspace);
-    // q_args for the fields a config decides; the workspace regions are this unit's own layout
-    QArgs a = q_args(cfg, d_X, d_adj, d_n_batch, params, workspace);
-    a.feat = reinterpret_cast<float*>(ws + lay.feat);
-    for (int l = 0; l < L; ++l) {
-        a.ppart[l] = reinterpret_cast<float*>(ws + lay.ppart[l]);
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gws = reinterpret_cast<float*>(ws + lay.gws);
-    a.gfcw = grads[2 * L];
-    a.gfcb = grads[2 * L + 1];
+    QArgs a = q_args(cfg, d_X, d_adj, d_n_batch, params, workspace, lay);
+    q_set_grads(a, grads, L);
     a.err = d_err;
     a.tag = tag;
     QbBatch t{};
     // scalars combine in double and reach the kernels as fp32, as the reference's Python floats reach torch
     t.t_mean = (float)t_mean;
     t.t_div = (float)(t_std + 1e-8);  // scripts/train_ccn.py:42
-    t.dout = reinterpret_cast<float*>(ws + lay.dout);
+    t.dout = reinterpret_cast<float*>(ws + lay.extra);
     QbApply q{};
     q.h = opt_scalars(OPT, beta1_or_momentum, beta2, eps, weight_decay);
     for (int k = 0; k < nt; ++k) {
@@ -359,17 +227,9 @@ int qb_train(const hgnn_ccn_config* cfg, int batch, const float* d_X, const floa
     uint32_t* reject = reinterpret_cast<uint32_t*>(ws);
     HGNN_HOST_CHECK(hipMemsetAsync(reject, 0, 4 * (size_t)K, s));
     static bool attr = false;
-    if (!attr) {  // the kernel's static LDS counts against the same cap
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ccn2_small_batch<Q_CF, XENT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(Q_LDS_MAX - QB_STATIC));
-        (void)hipGetLastError();  // a refused opt-in shows at the launch, not here
-        attr = true;
-    }
+    q_lds_attr(&k_ccn2_small_batch<Q_CF, XENT>, attr, QB_STATIC);
     const size_t lds = q_lds_bytes(cfg->nmax);
-    const int nf = q_nf(cfg);
-    int np = 0;
-    for (int l = 0; l < L; ++l) np += (int)q_prow(cfg, l);
-    const int nfc = (a.n_out * nf + a.n_out + 3) / 4;
+    const int np = q_np(cfg), nfc = q_nfc(cfg);
     for (int k = 0; k < K; ++k) {
         const long long g0 = (long long)k * batch;
         const int B = (int)(G - g0 < batch ? G - g0 : batch);  // the last mini-batch may be shorter
@@ -402,7 +262,7 @@ int hgnn_ccn2_small_train_batch_supported(const hgnn_ccn_config* cfg) {
 }
 
 size_t hgnn_ccn2_small_train_batch_workspace_bytes(const hgnn_ccn_config* cfg, int batch) {
-    if (!hgnn_ccn2_small_train_batch_supported(cfg) || batch < 1 || cfg->bs < 1 || cfg->bs > QB_GMAX) return 0;
+    if (!hgnn_ccn2_small_train_batch_supported(cfg) || batch < 1 || cfg->bs < 1 || cfg->bs > Q_TRAIN_GMAX) return 0;
     return qb_layout(cfg, batch).total;
 }
 
@@ -414,23 +274,17 @@ int hgnn_ccn2_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind,
                                 int32_t* d_err, int32_t tag, void* stream) {
     if (!hgnn_ccn2_small_train_batch_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
     if (!d_X || !d_adj || !d_y || !params || !grads || !state1 || !d_steps || !d_stats || !d_out || !workspace ||
-        !d_err || tag <= 0 || tag >= (1 << 23) || batch < 1 || cfg->bs < 1 || cfg->bs > QB_GMAX ||
+        !d_err || tag <= 0 || tag >= (1 << 23) || batch < 1 || cfg->bs < 1 || cfg->bs > Q_TRAIN_GMAX ||
         (xent && cfg->n_out < 2))
         return HGNN_ERR_ARG;
     // the meters come from mse_block, which leaves the division out below its own threshold (normalize_data's
     // rule); the CCN rule always divides, so such a divisor is refused rather than silently treated differently
     if (!xent && (float)(t_std + 1e-8) < 1e-5f) return HGNN_ERR_ARG;
-#define QB_TRAIN(X, O)                                                                                              \
-    qb_train<X, O>(cfg, batch, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, \
-                   state2, d_steps, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err,   \
-                   tag, (hipStream_t)stream)
-    switch (kind) {
-        case HGNN_OPT_ADAMAX: return xent ? QB_TRAIN(true, HGNN_OPT_ADAMAX) : QB_TRAIN(false, HGNN_OPT_ADAMAX);
-        case HGNN_OPT_SGD: return xent ? QB_TRAIN(true, HGNN_OPT_SGD) : QB_TRAIN(false, HGNN_OPT_SGD);
-        case HGNN_OPT_ADAM: return xent ? QB_TRAIN(true, HGNN_OPT_ADAM) : QB_TRAIN(false, HGNN_OPT_ADAM);
-        default: return HGNN_ERR_ARG;
-    }
-#undef QB_TRAIN
+    return opt_dispatch(kind, xent, [&](auto X, auto O) {
+        return qb_train<X(), O()>(cfg, batch, d_X, d_adj, d_n_batch, d_y, X() ? 0.0 : t_mean, X() ? 1.0 : t_std, params,
+                                  grads, state1, state2, d_steps, beta1_or_momentum, beta2, eps, weight_decay, d_stats,
+                                  d_out, workspace, d_err, tag, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

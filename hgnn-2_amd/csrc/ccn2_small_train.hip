@@ -6,8 +6,9 @@ namespace {
 
 // The per-graph training loop of scripts/train_ccn.py:31-73 in one dispatch, as k_ccn1_small_train (ccn_small.hip)
 // does it for CCN-1D: ONE workgroup runs plan, forward, loss, backward and the optimizer step of graph 0, then of
-// graph 1 on the weights graph 0 left, ...  The pieces are k_ccn2_small_fwd's and k_ccn2_small_bwd's bodies (the
-// bs == 1 form: gradients written and reduced in the kernel), k_mse_loss's / xent_row's loss and adamax_elem.
+// graph 1 on the weights graph 0 left, ...  The pieces are the stages k_ccn2_small_fwd and k_ccn2_small_bwd are made
+// of (ccn2_small.h; the bs == 1 form: gradients written and reduced in the kernel), k_mse_loss's / xent_row's loss
+// and optim_at.
 // One graph region and one graph's ppart rows serve every graph (q_plan<true>: packed base 0); the readout
 // features never leave LDS.
 // Coherence: the block reads words it wrote itself earlier in the dispatch.  The parameter pointers it writes
@@ -15,11 +16,9 @@ namespace {
 // agent-scope load (c2_ld<true>), so none can ride the scalar cache; the level, dp, rdp, trd and ppart rows are
 // read at per-lane addresses (vector loads) behind the barriers the one-shot kernels already rely on, and a
 // __threadfence() + barrier stands on both sides of the optimizer pass.
-// The helpers are inlined at each call ([[clang::always_inline]]): two instantiations call each of them, and an
-// outlined node function would spill the wave's state around every call.
-constexpr int Q_TMAX = 2 * Q_LMAX + 2;  // parameter tensors: level weights and biases, fc weight and bias
-constexpr int Q_TRAIN_GMAX = 4096;      // graphs per dispatch
-constexpr int Q_OMAX = 256;             // n_out bound: the graph's out / dout row in static LDS
+// Stages 1, 2 and 4 are the shared stage functions of ccn2_small.h, instantiated with FR = true (agent-scope
+// parameter loads) -- except stage 4's level walk, which is q_backward's body written out (see there); the loss (3)
+// and the optimizer (5) are this kernel's own.
 constexpr size_t Q_TRAIN_STATIC = 4 * Q_OMAX + 8 * 8 + 64;  // sout, sred, sbad and alignment slack
 
 struct QTrain {
@@ -47,18 +46,11 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
     __shared__ uint32_t sbad;
     __shared__ double sred[8];
     __shared__ float sout[Q_OMAX];  // out[g], then dout
-    QGraph& g = *reinterpret_cast<QGraph*>(lds);
+    auto [g, w, sp, P] = q_carve(lds, a);  // P: forward P, backward dp
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    char* wbase = lds + q_al16(sizeof(QGraph)) + (size_t)wv * q_wave_bytes(a.nmax);
-    QWave& w = *reinterpret_cast<QWave*>(wbase);
-    short* sp = reinterpret_cast<short*>(wbase + q_al16(sizeof(QWave)));
-    float* P = reinterpret_cast<float*>(wbase + q_al16(sizeof(QWave)) + q_sp_bytes(a.nmax));  // forward P, backward dp
     const int f = a.f, h = a.h, L = a.L, nf = f + L * h, n_out = a.n_out;
     float* G = a.gws;  // the one graph region
-    float* dA = G + (long long)L * a.r2 * h;
-    float* dB = dA + a.r2 * h;
-    float* rdp = dB + a.r2 * h;
-    float* trd = rdp + a.r1 * h;
+    const QRegion rg = q_region(a, G);
     float run_l = 0.f, run_m = 0.f;  // the RunningAverages (thread 0)
     int applied = 0;                 // optimizer steps taken so far in this dispatch
     if (threadIdx.x == 0) {
@@ -71,49 +63,11 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
         uint32_t bad = 0;
         const int n = q_nodes(a, gi, bad);
         [[clang::always_inline]] bad |= q_plan<true>(a, gi, n, g);
-        for (int o = 32; o > 0; o >>= 1) bad |= (uint32_t)__shfl_xor((int)bad, o, 64);
-        if (lane == 0 && bad) atomicOr(&sbad, bad);
-        // 2. forward: k_ccn2_small_fwd's body on the current weights
-        [[clang::always_inline]] q_colsum(g, n, f, 0, [&](int r, int c, double& acc) {
-            const double d = g.deg[r];
-            const double wgt = d * d;
-            acc += wgt * (double)g.Xs[r * f + c];
-        });
-        for (int l = 0; l < L; ++l) {
-            const int cin = l == 0 ? f : h;
-            float* fout = G + (long long)l * a.r2 * h;
-            const float* fin = l == 0 ? nullptr : G + (long long)(l - 1) * a.r2 * h;
-            if (l == 0) c2_weights<Q_HC, CF, true>(reinterpret_cast<float(*)[Q_HC][CF]>(g.wc), a.W[l], cin, 0, h);
-            else c2_weights<Q_HC, Q_HC, true>(reinterpret_cast<float(*)[Q_HC][Q_HC]>(g.wc), a.W[l], cin, 0, h);
-            __syncthreads();
-            for (int i = wv; i < n; i += Q_NW) {
-                if (l == 0)
-                    [[clang::always_inline]] q_node_fwd<CF, 1, true, true>(a, g, w, sp, P, i, l, fin, cin, fout);
-                else
-                    [[clang::always_inline]] q_node_fwd<Q_HC, 8, false, true>(a, g, w, sp, P, i, l, fin, cin, fout);
-            }
-            __syncthreads();
-            [[clang::always_inline]] q_colsum(g, n, h, f + l * h,
-                                              [&](int r, int c, double& acc) { acc += (double)g.nsum[l][r][c]; });
-        }
-        // the readout features stay in g.vec for the fc gradient; out[g] is what the graph saw before its own
-        // update
-        for (int o = 0; o < n_out; ++o) {
-            double s = 0.0;
-            if ((int)threadIdx.x < Q_RT)
-                for (int k = threadIdx.x; k < nf; k += Q_RT)
-                    s += (double)c2_ld<true>(a.fcw + o * nf + k) * (double)g.vec[k];
-            s = wave_sum_d(s);
-            __syncthreads();
-            if (lane == 0 && wv < 4) sred[wv] = s;
-            __syncthreads();
-            if (threadIdx.x == 0) {
-                const double tt = sred[0] + sred[1] + sred[2] + sred[3];
-                const float ov = (float)(tt + (double)c2_ld<true>(a.fcb + o));
-                a.out[(long long)gi * n_out + o] = ov;
-                sout[o] = ov;
-            }
-        }
+        q_report(bad, sbad);
+        // 2. forward on the current weights; the readout features stay in g.vec for the fc gradient; out[g] is what
+        // the graph saw before its own update
+        q_forward<CF, true>(a, g, w, sp, P, n, G);
+        q_readout<true>(a, g, nf, sred, a.out + (long long)gi * n_out, sout);
         // a target that is no class index rejects the graph like a validation bit: set before the barrier the
         // read of sbad follows, so the branch below is block-uniform
         int ti = 0;
@@ -171,35 +125,21 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
                 t.stats[3] = run_m;
             }
         }
-        // 4. backward, k_ccn2_small_bwd's bs == 1 body on the plan and levels of the forward: dsum, the fc
-        // gradients, then per level the node pass, the parameter reduction and the gather.  No dX: the level-0
-        // terms that feed only dX and its sum are left out (q_node_bwd<.., DX = false>).
+        // 4. backward, the one-graph form on the plan and levels of the forward: the fc gradients, dsum, then the
+        // level walk with the parameter reduction.  No dX: the level-0 terms that feed only dX and its sum are left
+        // out (q_node_bwd<.., DX = false>).
         // The fc gradients come first: they read the readout features where the forward left them, in g.vec (the
         // floats the one-shot forward stores to its feat row), before dsum takes that row.
-        const float* dob = sout;
-        for (int q = wv; q < n_out * nf + n_out; q += Q_NW) {
-            double s = 0.0;
-            if (q < n_out * nf) {
-                const int o = q / nf, k = q % nf;
-                if (lane < 1) s += (double)dob[o] * (double)g.vec[k];
-            } else if (lane < 1) {
-                s += (double)dob[q - n_out * nf];
-            }
-            s = wave_sum_d(s);
-            if (lane == 0) {
-                if (q < n_out * nf) a.gfcw[q] = (float)s;
-                else a.gfcb[q - n_out * nf] = (float)s;
-            }
-        }
+        q_fc_grads(a, sout, g.vec, nf);
         __syncthreads();
-        for (int k = threadIdx.x; k < nf; k += Q_NT) {
-            float s = 0.f;
-            for (int o = 0; o < n_out; ++o) s = fmaf(dob[o], c2_ld<true>(a.fcw + o * nf + k), s);
-            g.vec[k] = s;
-        }
+        q_dsum<true>(a, g, sout, nf);
         __syncthreads();
-        float* dcur = dA;
-        float* dnext = dB;
+        // The level walk is q_backward<CF, true, false>(.., reduce = true) written out: measured against the parent
+        // commit's library, this kernel with the call was 0.8 to 0.9 % slower per graph on the classification arm of
+        // tools/ab_ccn_train.py --order 2, at or beyond the parent's own min-max spread, and level with the parent
+        // with the walk written here ("CCN-2D small-graph stages").  Keep the two in step.
+        float* dcur = rg.dA;
+        float* dnext = rg.dB;
         for (int l = L - 1; l >= 0; --l) {
             const int cin = l == 0 ? f : h;
             const int K = 18 * cin, stride = h * K + h;
@@ -214,10 +154,10 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
                 float* pp = pl + (long long)(g.base + i) * stride;
                 if (l == 0)
                     [[clang::always_inline]] q_node_bwd<CF, 1, true, false>(a, g, w, sp, P, i, dcur, dtop, Fl, fin, cin,
-                                                                            rdp, trd, pp, nullptr);
+                                                                            rg.rdp, rg.trd, pp, nullptr);
                 else
-                    [[clang::always_inline]] q_node_bwd<Q_HC, 8, false>(a, g, w, sp, P, i, dcur, dtop, Fl, fin, cin, rdp,
-                                                                        trd, pp, nullptr);
+                    [[clang::always_inline]] q_node_bwd<Q_HC, 8, false>(a, g, w, sp, P, i, dcur, dtop, Fl, fin, cin,
+                                                                        rg.rdp, rg.trd, pp, nullptr);
             }
             __syncthreads();
             for (int k = wv; k < stride; k += Q_NW) {  // k_ccn_param_reduce's order over the graph's nodes
@@ -232,8 +172,8 @@ __global__ void __launch_bounds__(Q_NT) k_ccn2_small_train(QArgs a, QTrain t) {
             }
             if (l > 0)
                 for (int j = wv; j < n; j += Q_NW)
-                    [[clang::always_inline]] q_node_gather(a, g, w, sp, j, dcur, rdp, trd, g.vec + f + (l - 1) * h,
-                                                           dnext);
+                    [[clang::always_inline]] q_node_gather(a, g, w, sp, j, dcur, rg.rdp, rg.trd,
+                                                           g.vec + f + (l - 1) * h, dnext);
             __syncthreads();
             float* x = dcur;
             dcur = dnext;
@@ -293,16 +233,11 @@ int q_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, co
         if (!params[k] || !grads[k] || !exp_avg[k] || (TWO && !exp_inf[k])) return HGNN_ERR_ARG;
     // the one-graph layout of the workspace and of the backward (gradients written directly); the kernel reads
     // graph g's data at index g
-    QArgs a = q_args(&one, d_X, d_adj, d_n_batch, params, d_ws);
+    QArgs a = q_args(&one, d_X, d_adj, d_n_batch, params, d_ws, q_layout(&one, 1));
     a.out = d_out;
     a.err = d_err;
     a.tag = tag;
-    for (int l = 0; l < cfg->layers; ++l) {
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gfcw = grads[2 * cfg->layers];
-    a.gfcb = grads[2 * cfg->layers + 1];
+    q_set_grads(a, grads, cfg->layers);
     QTrain t{};
     t.y = d_y;
     t.clr = d_clr;
@@ -325,12 +260,7 @@ int q_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, co
     t.stats = d_stats;
     t.G = cfg->bs;
     static bool attr = false;
-    if (!attr) {  // the kernel's static LDS counts against the same cap
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ccn2_small_train<Q_CF, XENT, OPT>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(Q_LDS_MAX - Q_TRAIN_STATIC));
-        (void)hipGetLastError();  // a refused opt-in shows at the launch, not here
-        attr = true;
-    }
+    q_lds_attr(&k_ccn2_small_train<Q_CF, XENT, OPT>, attr, Q_TRAIN_STATIC);
     HGNN_KLAUNCH((k_ccn2_small_train<Q_CF, XENT, OPT>), dim3(1), dim3(Q_NT), q_lds_bytes(one.nmax), (hipStream_t)stream, a,
                  t);
     HGNN_LAUNCH_CHECK();
@@ -382,17 +312,11 @@ int hgnn_ccn2_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, co
                               int32_t tag, void* stream) {
     hgnn_ccn_config one;
     if (!q_train_ok(cfg, one)) return HGNN_ERR_UNSUPPORTED;
-#define Q_TRAIN_OPT(X, O)                                                                                          \
-    q_train<X, O>(cfg, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, state2, \
-                  d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err, tag,  \
-                  stream)
-    switch (kind) {
-        case HGNN_OPT_ADAMAX: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_ADAMAX) : Q_TRAIN_OPT(false, HGNN_OPT_ADAMAX);
-        case HGNN_OPT_SGD: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_SGD) : Q_TRAIN_OPT(false, HGNN_OPT_SGD);
-        case HGNN_OPT_ADAM: return xent ? Q_TRAIN_OPT(true, HGNN_OPT_ADAM) : Q_TRAIN_OPT(false, HGNN_OPT_ADAM);
-        default: return HGNN_ERR_ARG;
-    }
-#undef Q_TRAIN_OPT
+    return opt_dispatch(kind, xent, [&](auto X, auto O) {
+        return q_train<X(), O()>(cfg, d_X, d_adj, d_n_batch, d_y, X() ? 0.0 : t_mean, X() ? 1.0 : t_std, params, grads,
+                                 state1, state2, d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats,
+                                 d_out, workspace, d_err, tag, stream);
+    });
 }
 
 }  // extern "C"

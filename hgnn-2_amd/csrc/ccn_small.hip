@@ -598,16 +598,11 @@ int hgnn_ccn_small_train_opt(const hgnn_ccn_config* cfg, int kind, int xent, con
                              double weight_decay, float* d_stats, float* d_out, int32_t* d_err, int32_t tag,
                              void* stream) {
     if (!hgnn_ccn_small_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
-#define CS_TRAIN_OPT(X, O)                                                                                          \
-    cs_train<X, O>(cfg, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, state2, \
-                   d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, d_err, tag, stream)
-    switch (kind) {
-        case HGNN_OPT_ADAMAX: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_ADAMAX) : CS_TRAIN_OPT(false, HGNN_OPT_ADAMAX);
-        case HGNN_OPT_SGD: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_SGD) : CS_TRAIN_OPT(false, HGNN_OPT_SGD);
-        case HGNN_OPT_ADAM: return xent ? CS_TRAIN_OPT(true, HGNN_OPT_ADAM) : CS_TRAIN_OPT(false, HGNN_OPT_ADAM);
-        default: return HGNN_ERR_ARG;
-    }
-#undef CS_TRAIN_OPT
+    return opt_dispatch(kind, xent, [&](auto X, auto O) {
+        return cs_train<X(), O()>(cfg, d_X, d_adj, d_n_batch, d_y, X() ? 0.0 : t_mean, X() ? 1.0 : t_std, params, grads,
+                                  state1, state2, d_steps, 2, beta1_or_momentum, beta2, eps, weight_decay, d_stats,
+                                  d_out, d_err, tag, stream);
+    });
 }
 
 }  // extern "C"

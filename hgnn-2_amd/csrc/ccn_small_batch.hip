@@ -353,17 +353,11 @@ int hgnn_ccn_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, 
     // the meters come from mse_block, which leaves the division out below its own threshold (normalize_data's
     // rule); the CCN rule always divides, so such a divisor is refused rather than silently treated differently
     if (!xent && (float)(t_std + 1e-8) < 1e-5f) return HGNN_ERR_ARG;
-#define CB_TRAIN(X, O)                                                                                              \
-    cb_train<X, O>(cfg, batch, d_X, d_adj, d_n_batch, d_y, X ? 0.0 : t_mean, X ? 1.0 : t_std, params, grads, state1, \
-                   state2, d_steps, beta1_or_momentum, beta2, eps, weight_decay, d_stats, d_out, workspace, d_err,   \
-                   tag, (hipStream_t)stream)
-    switch (kind) {
-        case HGNN_OPT_ADAMAX: return xent ? CB_TRAIN(true, HGNN_OPT_ADAMAX) : CB_TRAIN(false, HGNN_OPT_ADAMAX);
-        case HGNN_OPT_SGD: return xent ? CB_TRAIN(true, HGNN_OPT_SGD) : CB_TRAIN(false, HGNN_OPT_SGD);
-        case HGNN_OPT_ADAM: return xent ? CB_TRAIN(true, HGNN_OPT_ADAM) : CB_TRAIN(false, HGNN_OPT_ADAM);
-        default: return HGNN_ERR_ARG;
-    }
-#undef CB_TRAIN
+    return opt_dispatch(kind, xent, [&](auto X, auto O) {
+        return cb_train<X(), O()>(cfg, batch, d_X, d_adj, d_n_batch, d_y, X() ? 0.0 : t_mean, X() ? 1.0 : t_std, params,
+                                  grads, state1, state2, d_steps, beta1_or_momentum, beta2, eps, weight_decay, d_stats,
+                                  d_out, workspace, d_err, tag, (hipStream_t)stream);
+    });
 }
 
 }  // extern "C"

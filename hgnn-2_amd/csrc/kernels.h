@@ -1,6 +1,8 @@
 // Internal launch wrappers shared by the executor and the C-ABI layer.
 #pragma once
 
+#include <type_traits>
+
 #include "common.h"
 #include "switches.h"
 
@@ -606,6 +608,19 @@ __device__ __forceinline__ void optim_at(float* pp, float g, float* s1, float* s
         s1[q] = m;
         s2[q] = u;
         pp[q] = p;
+    }
+}
+
+// The run-time pair (optimizer kind, classification) of a training entry as compile-time constants:
+// fn(std::bool_constant<XENT>, std::integral_constant<int, HGNN_OPT_*>) -> int; an unknown kind is HGNN_ERR_ARG.
+template <typename F>
+int opt_dispatch(int kind, int xent, F&& fn) {
+    auto loss = [&](auto opt) { return xent ? fn(std::true_type{}, opt) : fn(std::false_type{}, opt); };
+    switch (kind) {
+        case HGNN_OPT_ADAMAX: return loss(std::integral_constant<int, HGNN_OPT_ADAMAX>{});
+        case HGNN_OPT_SGD: return loss(std::integral_constant<int, HGNN_OPT_SGD>{});
+        case HGNN_OPT_ADAM: return loss(std::integral_constant<int, HGNN_OPT_ADAM>{});
+        default: return HGNN_ERR_ARG;
     }
 }
 

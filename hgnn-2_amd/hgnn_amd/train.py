@@ -637,10 +637,8 @@ class CcnTrainStep(_Optimizer):
         self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
         if path in ("batch_fused", "batch_fused2d"):
             self._step_batch_fused(X, adj, n_batch, y, two=path == "batch_fused2d")
-        elif path == "batch":
-            self._step_batch_pieces(X, adj, n_batch, y)
-        elif path == "unfused":
-            self._step_unfused(X, adj, n_batch, y)
+        elif path in ("batch", "unfused"):
+            self._step_pieces(X, adj, n_batch, y, self.batch_size if path == "batch" else 1)
         else:
             self._step_fused(X, adj, n_batch, y, two=path == "fused2d")
         return self.stats
@@ -705,34 +703,6 @@ class CcnTrainStep(_Optimizer):
         if strict() and not _capturing():
             _word.check(True)
 
-    def _step_unfused(self, X, adj, n_batch, y):
-        lib = L.lib()
-        m = self.model
-        stream = L.stream_handle(X.device)
-        cls = self.classification
-        if not cls:
-            yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device: no per-graph host work
-        n_out = self.spec.n_out
-        for g in range(X.shape[0]):
-            for p in self.params:
-                p.grad = None
-            out = m.forward_batch(X[g:g + 1], adj[g:g + 1], None if n_batch is None else n_batch[g:g + 1])
-            dout = torch.empty_like(out)
-            if cls:  # the output viewed as (1, n_out) (train_ccn.py:57): one row of n_out classes
-                L.check(lib.hgnn_xent_loss(L.ptr(out.detach()), L.ptr(y[g:g + 1]), 1, n_out, L.ptr(self.stats),
-                                           L.ptr(dout), L.ptr(self._targets.dev), stream), "cross-entropy loss")
-            else:
-                L.check(lib.hgnn_mse_loss(L.ptr(out.detach()), L.ptr(yn[g]), n_out, 0.0, 1.0, L.ptr(self.stats),
-                                          L.ptr(dout), stream), "mse loss")
-            torch.autograd.backward(out, dout)
-            grads = [p.grad for p in self.params]
-            if any(gr is None for gr in grads):
-                raise RuntimeError("hgnn_amd: a parameter received no gradient")
-            self._optim_step(lib, grads, stream)
-            self.out[g].copy_(out.detach()[0])
-        if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
-            self._targets.watch()
-
     def _workspace_batch2d(self, nmax, dev):
         """hgnn_ccn2_small_train_batch's workspace for chunks padded to nmax nodes: batch_size graph regions of about
         0.8 MB each at nmax = 29, layers = 2, hidden = 2 (so about 200 MB at batch_size = 256), allocated once per
@@ -787,17 +757,18 @@ class CcnTrainStep(_Optimizer):
         if strict() and not _capturing():
             _word.check(True)
 
-    def _step_batch_pieces(self, X, adj, n_batch, y):
-        """Mini-batch mode from the library's own pieces, per mini-batch: forward_batch, hgnn_mse_loss on the
-        device-normalised target with (0, 1) -- n = B n_out -- or hgnn_xent_loss with n = B, autograd backward,
-        hgnn_optim_step."""
+    def _step_pieces(self, X, adj, n_batch, y, B):
+        """One step per B consecutive graphs from the library's own pieces: forward_batch, hgnn_mse_loss on the
+        device-normalised target with (0, 1) -- n = B n_out -- or hgnn_xent_loss with n = B rows of n_out classes
+        (B = 1: the output viewed as (1, n_out), train_ccn.py:57), autograd backward, hgnn_optim_step.  B = 1 is
+        the per-graph loop (path "unfused"), B = batch_size the mini-batch mode (path "batch")."""
         lib = L.lib()
         m = self.model
         stream = L.stream_handle(X.device)
         cls = self.classification
         if not cls:
-            yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device
-        n_out, B = self.spec.n_out, self.batch_size
+            yn = (y - self._mean) / self._div  # train_ccn.py:42, on the device: no per-graph host work
+        n_out = self.spec.n_out
         for g0 in range(0, X.shape[0], B):
             g1 = min(g0 + B, X.shape[0])
             for p in self.params:
@@ -816,7 +787,7 @@ class CcnTrainStep(_Optimizer):
                 raise RuntimeError("hgnn_amd: a parameter received no gradient")
             self._optim_step(lib, grads, stream)
             self.out[g0:g1].copy_(out.detach())
-        if cls:  # the word is sticky: one look after the list
+        if cls:  # the word is sticky: one look after the list (HGNN_STRICT=1: a host sync here, none per graph)
             self._targets.watch()
 
     def check_targets(self):

@@ -5,7 +5,7 @@ QM9-shape graphs alternate between three paths,
   unfused   hgnn_amd.train.CcnTrainStep(fused=False): forward_batch, hgnn_mse_loss, backward, hgnn_adamax_step
   fused     CcnTrainStep(fused=True): hgnn_ccn_small_train, one dispatch per epoch
 
-each on its own copy of CCN_1D(5, 1, 2, 2).  Per path the min and median ms per graph over the epochs, printed
+each on its own copy of CCN_1D(5, 1, 2, 2).  Per path the min, median and max ms per graph over the epochs, printed
 as one JSON line and written to profiles/ccn_train_ab.json.  The tool holds no expectation.
 
 --loss xent: the classification branch (train_ccn.py:39-41, 56-57) on the generated driver's task
@@ -158,8 +158,8 @@ def main():
             torch.cuda.synchronize()
             if it >= 2:
                 times[k].append((time.perf_counter() - t0) * 1e3 / len(graphs))
-    res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5)}
-           for k, v in times.items()}
+    res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5),
+                                 "max": round(max(v), 5)} for k, v in times.items()}
     res["loss"] = "xent" if xent else "mse"
     res["order"] = args.order
     res["fused_path"] = steps["fused"].path
