@@ -2,9 +2,12 @@
 // the per-graph training loop) and ccn_small_batch.hip (the mini-batch training step): the LDS layout, the staging
 // round, the plan, one level of the forward and of the backward walk, the readout sums and the fc row.  Two
 // translation units, so that the mini-batch kernels' extra callers leave the other kernels' inlining, and with it
-// their code, alone.
+// their code, alone.  The kernels themselves are templates in ccn_small_kernels.h and ccn_small_batch_kernels.h; their
+// SPILL instantiations (ccn_small_spill.hip, ccn_small_batch_spill.hip) keep the row-sized arrays in global memory
+// and take this code as it is, bar the three places marked SPILL below.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -52,6 +55,33 @@ struct CsArgs {
         if (a.prof && blockIdx.x == 0 && threadIdx.x == 0) a.prof[k] = clock64(); \
     } while (0)
 
+// The SPILL instantiation (ccn_small_spill.hip, ccn_small_batch_spill.hip): the four row-sized arrays (F, dcoll,
+// dF0, dF1) of workgroup blockIdx.x live in region blockIdx.x of a caller-allocated global workspace instead of
+// LDS, so the graph size is no longer bounded by the depth.  A region is written and read by its workgroup only,
+// at per-lane addresses, behind the barriers the kernels have anyway (as ccn2_small.h's graph regions are).
+struct CsSpillArgs : CsArgs {
+    float* rows;         // regions of `rstride` floats, each 256-byte aligned
+    long long rstride;
+};
+template <bool SPILL>
+using CsArgsT = std::conditional_t<SPILL, CsSpillArgs, CsArgs>;
+
+// Tail padding of a region, in floats.  The LDS carve's CS_CF floats cover the level walks' reads past a row; the
+// backward's node pass also reads dF at row off1[i] + p for every lane p < G of node i, the graph's rows or not
+// (idle lanes, dropped by the selects): up to rcap + 62 rows of hidden channels plus CS_CF - 1.  LDS answers such
+// a read with whatever is there; a global read must stay inside the allocation.
+constexpr int CS_SPILL_PAD = 64 * CS_CF;
+
+// floats of one region: the LDS carve's order and strides (cs_carve, backward form), the padding, to 256 bytes
+__host__ __device__ inline size_t cs_spill_stride(int rcap, int f, int h, int L) {
+    const int cmax = f > h ? f : h;
+    const size_t fl = (size_t)rcap * ((size_t)h * L + 2 * cmax + 2 * h) + CS_SPILL_PAD;
+    return (fl + 63) / 64 * 64;
+}
+
+// LDS of a SPILL kernel: the fixed arrays and the staged adjacency (which aliases F in the LDS kernels)
+__host__ __device__ inline size_t cs_spill_lds_bytes(int rcap) { return CS_FIXED + 4 * (size_t)rcap + 4 * CS_CF; }
+
 struct CsLds {
     unsigned long long* bits;  // [64] row bit sets
     int* deg;                  // [64]
@@ -76,7 +106,8 @@ __host__ __device__ inline size_t cs_lds_bytes(int rcap, int f, int h, int L, bo
     return CS_FIXED + 4 * (size_t)rcap * (bwd ? (size_t)h * L + 2 * cmax + 2 * h : 2 * (size_t)h) + 4 * CS_CF;
 }
 
-__device__ inline CsLds cs_carve(char* base, const CsArgs& a, bool bwd) {
+template <bool SPILL = false>
+__device__ inline CsLds cs_carve(char* base, const CsArgsT<SPILL>& a, bool bwd) {
     CsLds s;
     size_t o = 0;
     s.bits = reinterpret_cast<unsigned long long*>(base + o);
@@ -97,6 +128,15 @@ __device__ inline CsLds cs_carve(char* base, const CsArgs& a, bool bwd) {
     o += 4 * CS_XMAX;
     s.Ws = reinterpret_cast<float*>(base + o);
     o += 4 * CS_WMAX;
+    if constexpr (SPILL) {  // one address space per instantiation: the rows in this workgroup's region
+        float* r = a.rows + (size_t)blockIdx.x * a.rstride;
+        const int cmax = a.f > a.h ? a.f : a.h;
+        s.F = r;
+        s.dcoll = s.F + (size_t)a.rcap * a.h * a.L;
+        s.dF0 = s.dcoll + (size_t)a.rcap * 2 * cmax;
+        s.dF1 = s.dF0 + (size_t)a.rcap * a.h;
+        return s;
+    }
     s.F = reinterpret_cast<float*>(base + o);
     o += 4 * (size_t)a.rcap * a.h * (bwd ? a.L : 2);
     s.dcoll = s.dF0 = s.dF1 = nullptr;
@@ -109,6 +149,13 @@ __device__ inline CsLds cs_carve(char* base, const CsArgs& a, bool bwd) {
         s.dF1 = reinterpret_cast<float*>(base + o);
     }
     return s;
+}
+
+// where cs_stage puts the adjacency block: over F (dead until level 0 writes it, after the plan), SPILL: LDS of its own
+template <bool SPILL = false>
+__device__ __forceinline__ float* cs_adj(char* base, const CsLds& s) {
+    if constexpr (SPILL) return reinterpret_cast<float*>(base + CS_FIXED);
+    else return s.F;
 }
 
 __device__ __forceinline__ uint32_t wave_or(uint32_t v) {
@@ -207,6 +254,25 @@ __device__ uint32_t cs_plan(int n, const CsLds& s, const float* As) {
     return bad;
 }
 
+// SPILL: where a walk reads either an LDS array or a row array by a block-uniform choice, the two pointers carry
+// their address spaces, so the choice stays a branch between an LDS and a global load (as plain pointers the
+// compiler folds it into one select of the two, and every such load becomes a flat load).
+typedef const __attribute__((address_space(3))) float* CsLdsPtr;
+typedef const __attribute__((address_space(1))) float* CsGlobalPtr;
+
+// cs_collect's batch of loads from one base (SPILL)
+template <int CF, typename P>
+__device__ __forceinline__ void cs_rows(P src, const int (&a1)[4], const int (&a2)[4], float (&t1)[4][CF],
+                                        float (&t2)[4][CF]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int c = 0; c < CF; ++c) {
+            t1[q][c] = src[a1[q] + c];
+            t2[q][c] = src[a2[q] + c];
+        }
+}
+
 // Level walks pack several nodes into a wave: G lanes per node (G = the power of two >= the graph's largest
 // receptive field, off1[66]), lane p of group g serves position / neighbour p of node i = base + wv * 64/G + g
 // (-1 past the graph).  A QM9 graph (d <= 5, G = 8) takes 8 nodes per wave: one pass of the 8 waves.
@@ -225,7 +291,7 @@ __device__ __forceinline__ CsSlot cs_slot(int base, int G, int n) {
 // neighbours -- no cross-lane reduction -- in the order of k_ccn1_fwd's one-chunk path.  Branch-free: the
 // four neighbours' ids, their rows and offsets, then every channel of both reads go out as one batch of LDS
 // loads each (reads past a row are discarded by the selects; cs_lds_bytes pads the allocation for them).
-template <int CF>
+template <int CF, bool SPILL = false>
 __device__ __forceinline__ void cs_collect(const CsLds& s, CsSlot sl, int G, const float* __restrict__ Xg,
                                            const float* Fin, int cin, float (&rs)[CF], float (&colv)[CF]) {
     const int ib = (sl.i >= 0 ? sl.i : 0) * 64;
@@ -261,13 +327,18 @@ __device__ __forceinline__ void cs_collect(const CsLds& s, CsSlot sl, int G, con
             a2[q] = lv0 ? wl * cin : (ol + __popcll(ml & ((1ull << jk[q]) - 1ull))) * cin;
         }
         float t1[4][CF], t2[4][CF];
+        if constexpr (SPILL) {  // Xg is LDS, Fin global: a block-uniform branch
+            if (lv0) cs_rows<CF>((CsLdsPtr)Xg, a1, a2, t1, t2);
+            else cs_rows<CF>((CsGlobalPtr)Fin, a1, a2, t1, t2);
+        } else {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
+            for (int q = 0; q < 4; ++q)
 #pragma unroll
-            for (int c = 0; c < CF; ++c) {
-                t1[q][c] = B[a1[q] + c];
-                t2[q][c] = B[a2[q] + c];
-            }
+                for (int c = 0; c < CF; ++c) {
+                    t1[q][c] = B[a1[q] + c];
+                    t2[q][c] = B[a2[q] + c];
+                }
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -299,13 +370,13 @@ __device__ __forceinline__ void cs_update(const CsLds& s, CsSlot sl, const float
 }
 
 // One level of the forward walk: F_l of every node (CF = the level's channel bound)
-template <int CF>
+template <int CF, bool SPILL = false>
 __device__ __forceinline__ void cs_fwd_level(const CsLds& s, int n, int G, const float* Xg, const float* fin, int cin,
                                              const float* Wl, int h, float* fout) {
     for (int base = 0; base < n; base += CS_NW * (64 / G)) {
         const CsSlot sl = cs_slot(base, G, n);
         float rs[CF], colv[CF];
-        cs_collect<CF>(s, sl, G, Xg, fin, cin, rs, colv);
+        cs_collect<CF, SPILL>(s, sl, G, Xg, fin, cin, rs, colv);
         cs_update<CF>(s, sl, rs, colv, cin, Wl, Wl + h * 2 * cin, h, fout);
     }
 }
@@ -363,7 +434,7 @@ __device__ __forceinline__ double cs_fc(const CsArgs& a, const CsLds& s, int o, 
 // One level of the backward walk (node pass, parameter gradients, gather), CF = this level's channel
 // bound (levels of hidden <= 2 take CF = 2: a quarter of the loads and selects of the 8-channel form).
 // DX = false (the training kernel, which needs no input gradient): level 0 ends after its parameter gradients.
-template <int CF, int CH, bool DX = true>
+template <int CF, int CH, bool DX = true, bool SPILL = false>
 __device__ void cs_bwd_level(const CsArgs& a, const CsLds& s, int b, int l, int n, int G, const float* Xg,
                              const float* dFc, float* dFn) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -388,14 +459,16 @@ __device__ void cs_bwd_level(const CsArgs& a, const CsLds& s, int b, int l, int 
     for (int base = 0; base < n; base += CS_NW * (64 / G)) {
         const CsSlot sl = cs_slot(base, G, n);
         float rs[CF], colv[CF];
-        cs_collect<CF>(s, sl, G, Xg, fin, cin, rs, colv);
+        cs_collect<CF, SPILL>(s, sl, G, Xg, fin, cin, rs, colv);
         const int ii = sl.i >= 0 ? sl.i : 0;
         const bool vx = sl.i >= 0 && sl.p < s.deg[ii];
         const int row = s.off1[ii] + sl.p;
         float dp[CH];
 #pragma unroll
         for (int o = 0; o < CH; ++o) {
-            const float g = top ? dtop[o] : dFc[row * h + o];  // unconditional LDS reads
+            float g;
+            if constexpr (SPILL) g = top ? ((CsLdsPtr)dtop)[o] : ((CsGlobalPtr)dFc)[row * h + o];
+            else g = top ? dtop[o] : dFc[row * h + o];  // unconditional LDS reads
             dp[o] = (vx && o < h && Fl[row * h + o] > 0.f) ? g : 0.f;
             ab[o] += dp[o];
 #pragma unroll

@@ -274,6 +274,17 @@ SIGNATURES = {
     "hgnn_ccn_small_train_batch": ([ctypes.POINTER(CcnConfig), _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,
                                     ctypes.c_double, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _VP, _I, _VP], _I),
+    "hgnn_ccn_small_spill_supported": ([ctypes.POINTER(CcnConfig)], _I),
+    "hgnn_ccn_small_spill_train_supported": ([ctypes.POINTER(CcnConfig)], _I),
+    "hgnn_ccn_small_spill_workspace_bytes": ([ctypes.POINTER(CcnConfig), _I], ctypes.c_size_t),
+    "hgnn_ccn_small_spill_forward": ([ctypes.POINTER(CcnConfig), _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP], _I),
+    "hgnn_ccn_small_spill_backward": ([ctypes.POINTER(CcnConfig), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP], _I),
+    "hgnn_ccn_small_spill_train": ([ctypes.POINTER(CcnConfig), _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,
+                                    ctypes.c_double, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double,
+                                    ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _VP, _I, _VP], _I),
+    "hgnn_ccn_small_spill_train_batch": ([ctypes.POINTER(CcnConfig), _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,
+                                          ctypes.c_double, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _I, _VP], _I),
     "hgnn_ccn2_small_train_batch_supported": ([ctypes.POINTER(CcnConfig)], _I),
     "hgnn_ccn2_small_train_batch_workspace_bytes": ([ctypes.POINTER(CcnConfig), _I], ctypes.c_size_t),
     "hgnn_ccn2_small_train_batch": ([ctypes.POINTER(CcnConfig), _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.c_double,

@@ -30,8 +30,15 @@ from .net import (_capturing, _require_cuda, _f32, _i64, _raise_bits, check_erro
 # CCN_1D on graphs of <= 64 nodes and CCN_2D on graphs of <= 32 nodes through the one-workgroup-per-graph
 # kernels (csrc/ccn_small.hip, csrc/ccn2_small.hip): no plan, no workspace sizing, 1 + 1 dispatches per call
 # for one graph.  HGNN_CCN_SMALL=0 (or setting this to False) keeps every call on the general path.
+# (small="spill", chosen per call, is the CCN_1D kernels' second form for shapes their LDS layout does not hold.)
 SMALL = os.environ.get("HGNN_CCN_SMALL", "1") != "0"
 SMALL2_WS_CAP = 512 << 20  # bytes: the CCN-2D small path's workspace bound per call (CcnSpec.small)
+
+# small="spill": the workspace bound per one-shot call.  A row region is nmax^2 (hidden layers + 2 max(f_in, hidden)
+# + 2 hidden) floats -- 2.5 MB at the bounds (64, 8, 8, 15), 0.25 MB at the generated-data driver's (50, 5, 2, 8) --
+# and a call needs one per graph, whatever the graphs' real sizes: like SMALL2_WS_CAP, the cap keeps a large batch
+# from silently taking gigabytes (512 MiB is 200 graphs at the bounds, 2000 at the driver's shape); cut the batch.
+SPILL_WS_CAP = 512 << 20
 
 CCN_MAX_DEGREE = {1: 1024, 2: 256}  # csrc/ccn_general.h CCN1_MAXD, CCN_BIGD (by order)
 CCN2_MAX_CHANNELS = 16  # csrc/ccn_general.h C2_CMAX_WIDE: CCN-2D f_in and hidden
@@ -66,6 +73,30 @@ class CcnSpec:
                 c = False
             self._small[key] = c
         return c or None
+
+    def spill(self, bs, nmax):
+        """(config, workspace bytes) of the spill instantiation of the CCN-1D small-graph kernels (small="spill");
+        raises where hgnn_ccn_small_spill_supported refuses or the workspace would exceed SPILL_WS_CAP."""
+        cfg = self.config(bs, nmax)
+        lib = L.lib()
+        if not lib.hgnn_ccn_small_spill_supported(ctypes.byref(cfg)):
+            raise RuntimeError(f"hgnn_amd: small=\"spill\" needs CCN_1D with graphs of 1 .. 64 nodes, input_feats and "
+                               f"hidden_size <= 8 and <= 15 layers (hgnn_ccn_small_spill_supported); got order "
+                               f"{self.order}, nmax {nmax}, input_feats {self.f_in}, hidden_size {self.hidden}, "
+                               f"{self.layers} layers")
+        nbytes = lib.hgnn_ccn_small_spill_workspace_bytes(ctypes.byref(cfg), bs)
+        if nbytes == 0 or nbytes > SPILL_WS_CAP:
+            raise RuntimeError(f"hgnn_amd: small=\"spill\" would need a workspace of {nbytes} bytes for {bs} graphs "
+                               f"padded to {nmax} nodes (one row region per graph), above SPILL_WS_CAP = "
+                               f"{SPILL_WS_CAP}: cut the batch")
+        return cfg, nbytes
+
+    def spill_max_batch(self, nmax):
+        """Graphs per small="spill" call padded to nmax nodes that stay within SPILL_WS_CAP (at least 1; spill()
+        still decides)."""
+        cfg = self.config(2, nmax)
+        two = L.lib().hgnn_ccn_small_spill_workspace_bytes(ctypes.byref(cfg), 2)
+        return max(1, SPILL_WS_CAP // (two // 2 + 256)) if two else 1
 
     def param_shapes(self):
         m = 2 if self.order == 1 else 18
@@ -211,45 +242,77 @@ register_check(_word.check)
 class _CcnSmallFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec, small, X, adj, n_batch, *params):
-        lib = L.lib()
-        cfg, ws_bytes = small
-        bs = X.shape[0]
-        s = L.stream_handle(X.device)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
-        out = torch.empty(bs, spec.n_out, dtype=torch.float32, device=X.device)
-        err, tag = _word.next(X.device)
-        L.check(lib.hgnn_ccn_small_forward(ctypes.byref(cfg), L.ptr(X), L.ptr(adj), L.ptr(n_batch),
-                                           L.ptr_array(params), L.ptr(ws), err, tag, L.ptr(out), s),
-                "hgnn_ccn_small_forward")
-        if strict() and not _capturing():
-            _word.check(True)
-        # the backward rebuilds the levels from X, adj, n_batch and the weights: saved through autograd so
-        # an in-place change between forward and backward raises instead of giving wrong gradients
-        ctx.save_for_backward(X, adj, n_batch, *params)
-        ctx.cfg, ctx.ws = cfg, ws
-        return out
+        return _small_forward("hgnn_ccn_small_forward", ctx, spec, small, X, adj, n_batch, *params)
 
     @staticmethod
     def backward(ctx, dout):
-        lib = L.lib()
-        X, adj, nb, *params = ctx.saved_tensors
-        dout = dout.contiguous()
-        dev = dout.device
-        grads = [torch.empty_like(p) for p in params]
-        dX = torch.empty(X.shape, dtype=torch.float32, device=dev)
-        L.check(lib.hgnn_ccn_small_backward(ctypes.byref(ctx.cfg), L.ptr(X), L.ptr(adj), L.ptr(nb),
-                                            L.ptr_array(params), L.ptr(ctx.ws), L.ptr(dout), L.ptr_array(grads),
-                                            L.ptr(dX), L.stream_handle(dev)), "hgnn_ccn_small_backward")
-        return (None, None, dX, None, None, *grads)
+        return _small_backward("hgnn_ccn_small_backward", ctx, dout)
 
 
-def run_ccn(spec, params, X, adj, n_batch, plan=None):
+class _CcnSpillFn(torch.autograd.Function):
+    """small="spill": the same call through hgnn_ccn_small_spill_forward / _backward -- the same validation word, the
+    same saved tensors; the workspace also holds one row region per graph (a third element of `small`: a
+    caller-provided workspace, 256-byte aligned and of the queried size)."""
+
+    @staticmethod
+    def forward(ctx, spec, small, X, adj, n_batch, *params):
+        return _small_forward("hgnn_ccn_small_spill_forward", ctx, spec, small, X, adj, n_batch, *params)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return _small_backward("hgnn_ccn_small_spill_backward", ctx, dout)
+
+
+def _small_forward(entry, ctx, spec, small, X, adj, n_batch, *params):
+    lib = L.lib()
+    cfg, ws_bytes = small[:2]
+    bs = X.shape[0]
+    s = L.stream_handle(X.device)
+    ws = small[2] if len(small) > 2 else torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
+    out = torch.empty(bs, spec.n_out, dtype=torch.float32, device=X.device)
+    err, tag = _word.next(X.device)
+    L.check(getattr(lib, entry)(ctypes.byref(cfg), L.ptr(X), L.ptr(adj), L.ptr(n_batch),
+                                L.ptr_array(params), L.ptr(ws), err, tag, L.ptr(out), s), entry)
+    if strict() and not _capturing():
+        _word.check(True)
+    # the backward rebuilds the levels from X, adj, n_batch and the weights: saved through autograd so
+    # an in-place change between forward and backward raises instead of giving wrong gradients
+    ctx.save_for_backward(X, adj, n_batch, *params)
+    ctx.cfg, ctx.ws = cfg, ws
+    return out
+
+
+def _small_backward(entry, ctx, dout):
+    lib = L.lib()
+    X, adj, nb, *params = ctx.saved_tensors
+    dout = dout.contiguous()
+    dev = dout.device
+    grads = [torch.empty_like(p) for p in params]
+    dX = torch.empty(X.shape, dtype=torch.float32, device=dev)
+    L.check(getattr(lib, entry)(ctypes.byref(ctx.cfg), L.ptr(X), L.ptr(adj), L.ptr(nb),
+                                L.ptr_array(params), L.ptr(ctx.ws), L.ptr(dout), L.ptr_array(grads),
+                                L.ptr(dX), L.stream_handle(dev)), entry)
+    return (None, None, dX, None, None, *grads)
+
+
+def run_ccn(spec, params, X, adj, n_batch, plan=None, small=None):
     """Batched CCN forward: X (bs,nmax,f), adj (bs,nmax,nmax), n_batch (bs,) -> (bs, n_out).
     plan: a CcnPlan of this adj / n_batch (else the plan is built here: without a host sync for
     small shapes, ASYNC_PLAN_BOUND; with one otherwise).  n_batch None: every graph has nmax nodes.
     CCN_1D batches of <= 64-node graphs and CCN_2D batches of <= 32-node graphs (f_in <= 8, hidden <= 2) take
-    the small-graph kernels (SMALL; a plan is then unused)."""
+    the small-graph kernels (SMALL; a plan is then unused).
+    small: None is that routing.  "spill" runs the spill instantiation of the CCN-1D small-graph kernels
+    (hgnn_ccn_small_spill_forward / _backward: the row arrays in a global workspace, so every CCN_1D shape within 64
+    nodes, 8 channels and 15 layers, whatever SMALL says; the LDS kernels' bits where both exist) and raises where
+    hgnn_ccn_small_spill_supported refuses or the workspace would exceed SPILL_WS_CAP."""
     check_errors(block=False)
+    if small is not None:
+        if small != "spill":
+            raise RuntimeError(f"hgnn_amd: small={small!r}: expected None or \"spill\"")
+        _require_cuda([X, adj, n_batch, *params], "CCN")
+        _check_shapes(spec, params, X, adj, n_batch)
+        return _CcnSpillFn.apply(spec, spec.spill(X.shape[0], X.shape[1]), _f32(X), _f32(adj),
+                                 None if n_batch is None else _i64(n_batch), *[_f32(p) for p in params])
     # the small-graph kernels need no plan: a batch planned for capture (CcnPlan) takes them too
     if SMALL and X.dim() == 3:
         small = spec.small(X.shape[0], X.shape[1])

@@ -381,6 +381,21 @@ CCN_TRAIN_BATCH_FUSED_DEFAULT = True
 # at both sizes, by 1.23 and 1.09 times (1.09 and 1.08 in a repeat of the run).  Switching the default is a later
 # change, and one that must also change tests/test_gpu_ccn_train_batch.py.
 CCN2_TRAIN_BATCH_FUSED_DEFAULT = False
+# Whether fused=None takes the spill instantiation of the CCN-1D kernels (fused="ccn1_spill": hgnn_ccn_small_spill_train
+# and hgnn_ccn_small_spill_train_batch, the row arrays in a global workspace) on chunks the LDS kernels refuse.  Off:
+# fused=None keeps such chunks on "unfused" / "batch", which tests/test_gpu_ccn_train.py and
+# tests/test_gpu_ccn_train_batch.py pin.  The measured A/B (tools/ab_ccn_train.py --spill,
+# profiles/ccn_train_spill_ab.json, DESIGN.md "CCN-1D small graphs past the LDS bound"), median (min, max) ms per graph:
+# (a) the routes it replaces, 256 three_collinear_points(n_max=50) graphs, CCN_1D(5, 2, 2, 8), classification: the loop
+# 0.5868 (0.5857, 0.5876) against unfused 0.3651 (0.3613, 0.4875); B = 32: 0.0565 (0.0562, 0.0567) against the pieces'
+# 0.0206 (0.0181, 0.0225); B = 256: 0.0078 (0.0077, 0.0081) against 0.0059 (0.0055, 0.0071) -- the spill route LOSES at
+# every setting (1.6, 2.7 and 1.3 times: dense 49-node graphs, eight levels of dependent L2 round trips in one
+# workgroup per graph).  Recommendation: leave it off; take it where one dispatch per chunk matters more than the time
+# (a captured epoch).  (b) its price on shapes the LDS kernels take, the 256 QM9-shape graphs, CCN_1D(5, 1, 2, 2): the
+# loop 0.0310 (0.0308, 0.0311) against 0.0287 (0.0287, 0.0288), B = 32: 0.0015 (0.0015, 0.0016) against 0.0017
+# (0.0017, 0.0019).
+# Switching the default is a later change, and one that must also change those tests.
+CCN1_TRAIN_SPILL_DEFAULT = False
 
 
 class CcnTrainStep(_Optimizer):
@@ -395,6 +410,11 @@ class CcnTrainStep(_Optimizer):
                graphs of <= 64 nodes, input_feats and hidden_size <= 8)
       fused2d  hgnn_ccn2_small_train: the same for CCN_2D (graphs of <= 32 nodes, input_feats <= 8,
                hidden_size <= 2, n_outputs <= 256); its one-graph workspace is allocated once per nmax and kept
+      fused_spill  hgnn_ccn_small_spill_train: the CCN_1D kernel with its row-sized arrays (the levels, dcoll, dF) in a
+               global workspace region instead of LDS -- fused="ccn1_spill", every CCN_1D chunk within
+               hgnn_ccn_small_spill_train_supported (graphs of <= 64 nodes, input_feats and hidden_size <= 8, <= 15
+               layers, whatever the depth).  The LDS kernel's arithmetic in its order: the same bits where both
+               exist.  Its one row region is allocated once per nmax and kept
       unfused  per graph forward_batch on the one-graph slice, hgnn_mse_loss, autograd backward and
                hgnn_optim_step: the same arithmetic from the separate entry points (larger graphs, wider
                channels)
@@ -402,8 +422,10 @@ class CcnTrainStep(_Optimizer):
     fused=None takes a fused kernel wherever hgnn_ccn_small_train_supported or hgnn_ccn2_small_train_supported
     allows it (the latter by CCN2_TRAIN_FUSED_DEFAULT, the measured default), fused=False never; fused=True means
     the CCN_1D kernel and raises where that is not supported (so for every CCN_2D model), fused="ccn2" means the
-    CCN_2D kernel and raises likewise.  After each step, .path says which of the three ran.  No path synchronises
-    with the host.
+    CCN_2D kernel and raises likewise; fused="ccn1_spill" means the spill instantiation, whatever nmax (also where
+    the LDS kernel would fit): it raises in the constructor on a model it cannot take (CCN_2D, wider channels, more
+    layers) and in step() on a chunk padded beyond 64 nodes, and its evaluate / eval_epoch go through
+    forward_batch(small="spill").  After each step, .path says which ran.  No path synchronises with the host.
 
     A graph the fused kernel rejects (missing self loop, asymmetric pattern, n_b outside [0, nmax]) takes no
     step and updates no meter; the error shows at the next check (hgnn_amd.net.check_errors(), or at once
@@ -419,8 +441,12 @@ class CcnTrainStep(_Optimizer):
     a fused kernel skips it like a rejected graph (no step), the unfused path does what TrainStep does (the
     row's dout is zero and the Adamax step is still taken, on zero gradients).
 
-    fused=None and classification: the kernel's backward LDS layout bounds the graph size by the depth (at the
-    generated driver's CCN_1D(5, 2, 2, 10): 31 nodes), so a chunk padded to a larger graph runs unfused.
+    Limit of fused=None / True: the LDS kernels' backward layout bounds the graph size by the depth (42 nodes at
+    CCN_1D(5, 2, 2, 2), 31 at the generated driver's CCN_1D(5, 2, 2, 10), 22 at hidden 8 with 4 layers), and a chunk is
+    padded to its largest graph, so one larger graph sends the whole chunk to "unfused" (mini-batch mode: "batch").
+    fused="ccn1_spill" has no such term: it takes those chunks in one dispatch (mini-batch mode: two per
+    mini-batch) at the price of global-memory rows.  It is opt-in (CCN1_TRAIN_SPILL_DEFAULT, the measured A/B beside
+    it).
 
     optimizer="adamax" (default) | "sgd" | "adam" and momentum (see _Optimizer; scripts/main_ccn.py:155-162): the
     fused paths are then hgnn_ccn_small_train_opt / hgnn_ccn2_small_train_opt, the same kernels with their optimizer
@@ -447,6 +473,10 @@ class CcnTrainStep(_Optimizer):
                    input_feats <= 8, hidden_size <= 2, n_outputs <= 256), B <= 4096.  Its workspace holds batch_size
                    graph regions (about 0.8 MB each at 29 nodes, two layers, hidden 2: about 200 MB at B = 256),
                    allocated once per nmax and kept
+      batch_fused_spill  hgnn_ccn_small_spill_train_batch: batch_fused's two dispatches with the row arrays of each
+                   workgroup in its own global region -- fused="ccn1_spill" with batch_size, bounds as fused_spill.
+                   The workspace holds batch_size row regions (nmax^2 (hidden layers + 2 max(input_feats, hidden) +
+                   2 hidden) floats each: 0.25 MB at 50 nodes, CCN_1D(5, 2, 2, 8)), allocated once per nmax and kept
       batch        the library's pieces per mini-batch: forward_batch, hgnn_mse_loss on the device-normalised target
                    with (0, 1) (or hgnn_xent_loss), autograd backward, hgnn_optim_step -- CCN_2D, larger graphs, wider
                    channels.  The same arithmetic bit for bit where both routes exist.
@@ -480,6 +510,11 @@ class CcnTrainStep(_Optimizer):
         self.batch_size = batch_size
         if not isinstance(model, _CCN):
             raise RuntimeError("hgnn_amd: CcnTrainStep needs a CCN_1D / CCN_2D model (TrainStep is the GNN step)")
+        if isinstance(fused, str) and fused == "ccn1_spill":  # host-only, like the next
+            cfg = model._spec().config(1, 1)
+            if not L.lib().hgnn_ccn_small_spill_train_supported(ctypes.byref(cfg)):
+                raise RuntimeError("hgnn_amd: fused=\"ccn1_spill\" needs CCN_1D with input_feats and hidden_size <= 8, "
+                                   "<= 15 layers and n_outputs <= 1088 (hgnn_ccn_small_spill_train_supported)")
         if isinstance(fused, str) and fused == "ccn2_batch":  # a host-only question: asked before the device's
             cfg = model._spec().config(1, 1)
             if not L.lib().hgnn_ccn2_small_train_batch_supported(ctypes.byref(cfg)):
@@ -513,9 +548,9 @@ class CcnTrainStep(_Optimizer):
         self.spec = model._spec()
         self.fused = fused
         if isinstance(fused, str):
-            if fused not in ("ccn2", "ccn2_batch"):
-                raise RuntimeError(f"hgnn_amd: fused={fused!r}: expected None, False, True, \"ccn2\" or "
-                                   "\"ccn2_batch\"")
+            if fused not in ("ccn2", "ccn2_batch", "ccn1_spill"):
+                raise RuntimeError(f"hgnn_amd: fused={fused!r}: expected None, False, True, \"ccn2\", "
+                                   "\"ccn2_batch\" or \"ccn1_spill\"")
             if fused == "ccn2" and not self._supported2d(1):
                 raise RuntimeError("hgnn_amd: fused=\"ccn2\" needs CCN_2D with input_feats <= 8, hidden_size <= 2 "
                                    "and n_outputs <= 256 (hgnn_ccn2_small_train_supported)")
@@ -524,11 +559,13 @@ class CcnTrainStep(_Optimizer):
                                "(hgnn_ccn_small_train_supported)")
         self.stats = torch.zeros(4, dtype=torch.float32, device=dev)
         self.out = None
-        # "fused", "fused2d" or "unfused" (mini-batch mode: "batch_fused", "batch_fused2d" or "batch"): the last step
+        # "fused", "fused2d", "fused_spill" or "unfused" (mini-batch mode: "batch_fused", "batch_fused2d",
+        # "batch_fused_spill" or "batch"): the last step
         self.path = None
         self._ws2d = {}   # nmax -> the CCN-2D kernel's one-graph workspace
         self._ws_batch = None  # hgnn_ccn_small_train_batch's workspace (sized once: it does not depend on nmax)
         self._ws_batch2d = {}  # nmax -> hgnn_ccn2_small_train_batch's workspace (batch_size graph regions)
+        self._ws_spill = {}    # (nmax, regions) -> the spill kernels' row regions (1: the loop, batch_size: mini-batches)
         self._grads = [torch.zeros_like(p) for p in self.params]
         self._numel = (ctypes.c_int64 * len(self.params))(*[p.numel() for p in self.params])
         # the target's shift and divisor as fp32 device scalars: (y - mean) / (std + 1e-8), a true division
@@ -562,9 +599,30 @@ class CcnTrainStep(_Optimizer):
         return self.batch_size <= CCN_TRAIN_MAX_GRAPHS and (self.classification
                                                             or f32(self.t_std + 1e-8) >= f32(1e-5))
 
+    def _supported_spill(self, nmax):
+        """Whether the spill kernels take chunks of this step padded to nmax nodes (mini-batch mode: with
+        _supported_batch's two host-side conditions)."""
+        cfg = self.spec.config(1, nmax)
+        if not L.lib().hgnn_ccn_small_spill_train_supported(ctypes.byref(cfg)):
+            return False
+        if self.batch_size is None:
+            return True
+        f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]  # noqa: E731
+        return self.batch_size <= CCN_TRAIN_MAX_GRAPHS and (self.classification
+                                                            or f32(self.t_std + 1e-8) >= f32(1e-5))
+
+    def _route_spill(self, nmax):
+        if not self._supported_spill(nmax):
+            what = "" if self.batch_size is None else f"batch_size = {self.batch_size} at "
+            raise RuntimeError(f"hgnn_amd: fused=\"ccn1_spill\", but {what}nmax = {nmax} is outside the spill kernels' "
+                               "bounds (hgnn_ccn_small_spill_train_supported: graphs of <= 64 nodes)")
+        return "fused_spill" if self.batch_size is None else "batch_fused_spill"
+
     def _route_batch(self, nmax):
         """The path of a chunk padded to nmax nodes in mini-batch mode."""
         fused = self.fused
+        if fused == "ccn1_spill":
+            return self._route_spill(nmax)
         if fused is None:
             if CCN_TRAIN_BATCH_FUSED_DEFAULT and self._supported_batch(nmax):
                 return "batch_fused"
@@ -587,6 +645,8 @@ class CcnTrainStep(_Optimizer):
         if self.batch_size is not None:
             return self._route_batch(nmax)
         fused = self.fused
+        if fused == "ccn1_spill":
+            return self._route_spill(nmax)
         if fused is None:
             one = CCN_TRAIN_FUSED_OPTIM.get((1, self.optimizer), True)
             two = CCN_TRAIN_FUSED_OPTIM.get((2, self.optimizer), CCN2_TRAIN_FUSED_DEFAULT)
@@ -635,12 +695,13 @@ class CcnTrainStep(_Optimizer):
         G, nmax = X.shape[0], X.shape[1]
         self.path = path = self._route(nmax)  # before the work: a strict check inside it may raise
         self.out = torch.empty(G, self.spec.n_out, dtype=torch.float32, device=X.device)
-        if path in ("batch_fused", "batch_fused2d"):
-            self._step_batch_fused(X, adj, n_batch, y, two=path == "batch_fused2d")
+        if path in ("batch_fused", "batch_fused2d", "batch_fused_spill"):
+            self._step_batch_fused(X, adj, n_batch, y, two=path == "batch_fused2d",
+                                   spill=path == "batch_fused_spill")
         elif path in ("batch", "unfused"):
             self._step_pieces(X, adj, n_batch, y, self.batch_size if path == "batch" else 1)
         else:
-            self._step_fused(X, adj, n_batch, y, two=path == "fused2d")
+            self._step_fused(X, adj, n_batch, y, two=path == "fused2d", spill=path == "fused_spill")
         return self.stats
 
     def _workspace2d(self, nmax, dev):
@@ -652,7 +713,19 @@ class CcnTrainStep(_Optimizer):
             self._ws2d[nmax] = ws
         return ws
 
-    def _step_fused(self, X, adj, n_batch, y, two=False):
+    def _workspace_spill(self, nmax, regions, dev):
+        """The spill kernels' row regions for chunks padded to nmax nodes (hgnn_ccn_small_spill_workspace_bytes with
+        bs = 1: the training entries use the regions only), allocated once per (nmax, regions) and kept, like
+        _ws_batch2d."""
+        ws = self._ws_spill.get((nmax, regions))
+        if ws is None:
+            cfg = self.spec.config(1, nmax)
+            ws = torch.empty(L.lib().hgnn_ccn_small_spill_workspace_bytes(ctypes.byref(cfg), regions),
+                             dtype=torch.uint8, device=dev)
+            self._ws_spill[(nmax, regions)] = ws
+        return ws
+
+    def _step_fused(self, X, adj, n_batch, y, two=False, spill=False):
         from .ccn import _word
         from .net import _capturing, check_errors, strict
         lib = L.lib()
@@ -662,9 +735,12 @@ class CcnTrainStep(_Optimizer):
         b1, b2 = self.betas
         # order 2: the kernel's one-graph workspace goes before the error word
         ws = (L.ptr(self._workspace2d(X.shape[1], dev)),) if two else ()
-        adamax = self.optimizer == "adamax"
+        adamax = self.optimizer == "adamax" and not spill
         name = "hgnn_ccn2_small_train" if two else "hgnn_ccn_small_train"
         name += ("_xent" if self.classification else "") if adamax else "_opt"
+        if spill:  # one entry for every optimizer and loss (the _opt form); its one row region before the error word
+            name = "hgnn_ccn_small_spill_train"
+            ws = (L.ptr(self._workspace_spill(X.shape[1], 1, dev)),)
         entry = getattr(lib, name)
         for g0 in range(0, X.shape[0], CCN_TRAIN_MAX_GRAPHS):
             g1 = min(g0 + CCN_TRAIN_MAX_GRAPHS, X.shape[0])
@@ -715,9 +791,10 @@ class CcnTrainStep(_Optimizer):
             self._ws_batch2d[nmax] = ws
         return ws
 
-    def _step_batch_fused(self, X, adj, n_batch, y, two=False):
-        """Mini-batch mode, hgnn_ccn_small_train_batch (two: hgnn_ccn2_small_train_batch): one call per run of whole
-        mini-batches within the entry's 4096-graph bound."""
+    def _step_batch_fused(self, X, adj, n_batch, y, two=False, spill=False):
+        """Mini-batch mode, hgnn_ccn_small_train_batch (two: hgnn_ccn2_small_train_batch, spill:
+        hgnn_ccn_small_spill_train_batch): one call per run of whole mini-batches within the entry's 4096-graph
+        bound."""
         from .ccn import _word
         from .net import _capturing, check_errors, strict
         lib = L.lib()
@@ -726,15 +803,21 @@ class CcnTrainStep(_Optimizer):
         stream = L.stream_handle(dev)
         B, G = self.batch_size, X.shape[0]
         name = "hgnn_ccn2_small_train_batch" if two else "hgnn_ccn_small_train_batch"
+        if spill:
+            name = "hgnn_ccn_small_spill_train_batch"
         entry = getattr(lib, name)
         if two:
             ws = self._workspace_batch2d(X.shape[1], dev)
         else:
             if self._ws_batch is None:
-                cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, X.shape[1])
+                # the layout does not depend on nmax; spill: asked at nmax = 1, where the LDS predicate of this
+                # query holds for every model the spill kernels take
+                cfg = self.spec.config(CCN_TRAIN_MAX_GRAPHS, 1 if spill else X.shape[1])
                 self._ws_batch = torch.empty(lib.hgnn_ccn_small_train_batch_workspace_bytes(ctypes.byref(cfg), B),
                                              dtype=torch.uint8, device=dev)
             ws = self._ws_batch
+        # spill: the mini-batch's row regions go after the workspace
+        rows = (L.ptr(self._workspace_spill(X.shape[1], B, dev)),) if spill else ()
         span = CCN_TRAIN_MAX_GRAPHS // B * B
         s1, s2 = self._states()
         for g0 in range(0, G, span):
@@ -749,7 +832,7 @@ class CcnTrainStep(_Optimizer):
                 ctypes.byref(cfg), B, self._kind, int(self.classification), L.ptr(X[g0:g1]), L.ptr(adj[g0:g1]),
                 L.ptr(None if n_batch is None else n_batch[g0:g1]), L.ptr(y[g0:g1]), self.t_mean, self.t_std,
                 L.ptr_array(self.params), L.ptr_array(self._grads), s1, s2, L.ptr(sc), self._b1(), self.betas[1],
-                self.eps, self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), L.ptr(ws), err,
+                self.eps, self.weight_decay, L.ptr(self.stats), L.ptr(self.out[g0:g1]), L.ptr(ws), *rows, err,
                 tag, stream), name)
             self.step_count += k
         for p, g in zip(self.params, self._grads):
@@ -804,7 +887,14 @@ class CcnTrainStep(_Optimizer):
         reference leaves it, and the fraction of graphs whose argmax is the target (hgnn_ccn_eval_xent)."""
         X, adj, n_batch, y = self._inputs(X, adj, n_batch, y)
         with torch.no_grad():
-            out = self.model.forward_batch(X, adj, n_batch).contiguous()
+            if self.fused == "ccn1_spill":
+                # one row region per graph of a call: slices that stay below the one-shot workspace cap
+                m = self.spec.spill_max_batch(X.shape[1])
+                out = torch.cat([self.model.forward_batch(X[g:g + m], adj[g:g + m],
+                                                          None if n_batch is None else n_batch[g:g + m], small="spill")
+                                 for g in range(0, X.shape[0], m)]).contiguous()
+            else:
+                out = self.model.forward_batch(X, adj, n_batch).contiguous()
         if self.classification:
             self._targets.poll(block=False)
             res = torch.empty(3, dtype=torch.float32, device=X.device)

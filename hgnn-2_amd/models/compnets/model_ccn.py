@@ -43,8 +43,9 @@ class _CCN(nn.Module):
         (hgnn_amd.ccn.CcnPlan; lets the step be captured in a HIP graph)."""
         return CcnPlan(self._spec(), adj, n_batch)
 
-    def forward_batch(self, X, adj, n_batch, plan=None):
-        return run_ccn(self._spec(), self._params(), X, adj, n_batch, plan)
+    def forward_batch(self, X, adj, n_batch, plan=None, small=None):
+        """small="spill": the CCN-1D small-graph kernels with their row arrays in global memory (run_ccn)."""
+        return run_ccn(self._spec(), self._params(), X, adj, n_batch, plan, small)
 
     def forward(self, X, adj):
         if X.dim() != 2 or adj.dim() != 2:

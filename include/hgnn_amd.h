@@ -640,6 +640,50 @@ int hgnn_ccn_small_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, 
                                float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
                                double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
                                int32_t* d_err, int32_t tag, void* stream);
+/* CCN-1D small graphs past the LDS bound (csrc/ccn_small_spill.hip, csrc/ccn_small_batch_spill.hip): a second
+ * instantiation of the kernels above whose four row-sized arrays (the L levels, dcoll, dF0, dF1) live in a
+ * per-workgroup region of a caller-allocated global workspace; everything else stays in LDS (at most 37.2 KB at
+ * nmax = 64).  The arithmetic and its order are those of the LDS kernels: bit for bit the same results wherever both
+ * exist.  Chosen per call -- no entry above ever routes here.
+ *   spill_supported: host only; 1 for order 1, 1 <= nmax <= 64, 1 <= f_in, hidden <= 8, 1 <= layers <= 15 (bs and
+ *     n_out positive), with no LDS-fit term; else 0 (NULL: 0).
+ *   spill_train_supported: the same with n_out <= 1088 (the training kernels' bound, as hgnn_ccn_small_train_supported); cfg->bs is not looked at.
+ *   spill_workspace_bytes(cfg, regions): host only.  `regions` row regions, then the feat / ppart part of
+ *     hgnn_ccn_small_workspace_bytes for cfg->bs graphs: regions * stride + align256(4 bs nf) + (bs > 1 ?
+ *     4 bs ptot : 0) bytes.  A region keeps the LDS carve's order and strides -- nmax^2 hidden floats per level,
+ *     nmax^2 2 max(f_in, hidden), nmax^2 hidden twice -- plus 512 floats of tail padding (the walks read rows of idle
+ *     lanes past the graph's and drop them; those reads stay inside the region), rounded up to 256 bytes:
+ *     stride = align256(4 (nmax^2 (hidden layers + 2 max(f_in, hidden) + 2 hidden) + 512)).
+ *     regions = cfg->bs for the one-shot calls, 1 for the training loop, `batch` for a mini-batch call (the training
+ *     entries use the regions only, so their cfg->bs may be 1 in the query).  0 for regions < 1, on overflow or
+ *     where spill_supported is 0.  The workspace must be 256-byte aligned; a region is written and read by its
+ *     workgroup only and nothing in it is read before it is written (apart from values the selects drop).
+ *   The entries mirror hgnn_ccn_small_forward / _backward, hgnn_ccn_small_train_opt and hgnn_ccn_small_train_batch
+ *     argument for argument, with the spill workspace added (`workspace` / `spill_workspace`; the mini-batch entry
+ *     still takes hgnn_ccn_small_train_batch_workspace_bytes' workspace as well), and return the same codes:
+ *     HGNN_ERR_UNSUPPORTED where the predicate is 0, HGNN_ERR_ARG for a null pointer and the other argument errors. */
+int hgnn_ccn_small_spill_supported(const hgnn_ccn_config* cfg);
+int hgnn_ccn_small_spill_train_supported(const hgnn_ccn_config* cfg);
+size_t hgnn_ccn_small_spill_workspace_bytes(const hgnn_ccn_config* cfg, int regions);
+int hgnn_ccn_small_spill_forward(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                                 const int64_t* d_n_batch, const float* const* params, void* workspace,
+                                 int32_t* d_err, int32_t tag, float* d_out, void* stream);
+int hgnn_ccn_small_spill_backward(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
+                                  const int64_t* d_n_batch, const float* const* params, void* workspace,
+                                  const float* d_dout, float* const* grads, float* d_dX, void* stream);
+int hgnn_ccn_small_spill_train(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,
+                               const int64_t* d_n_batch, const float* d_y, double t_mean, double t_std,
+                               float* const* params, float* const* grads, float* const* state1,
+                               float* const* state2, const float* d_steps, double beta1_or_momentum, double beta2,
+                               double eps, double weight_decay, float* d_stats, float* d_out, void* workspace,
+                               int32_t* d_err, int32_t tag, void* stream);
+int hgnn_ccn_small_spill_train_batch(const hgnn_ccn_config* cfg, int batch, int kind, int xent, const float* d_X,
+                                     const float* d_adj, const int64_t* d_n_batch, const float* d_y, double t_mean,
+                                     double t_std, float* const* params, float* const* grads, float* const* state1,
+                                     float* const* state2, const float* d_steps, double beta1_or_momentum,
+                                     double beta2, double eps, double weight_decay, float* d_stats, float* d_out,
+                                     void* workspace, void* spill_workspace, int32_t* d_err, int32_t tag,
+                                     void* stream);
 /* The same for CCN-2D (csrc/ccn2_small_batch.hip): mini-batches of `batch` graphs, one workgroup per graph, two
  * dispatches per mini-batch ordered by the stream alone.  The first runs plan, forward, the graph's dout row and the
  * backward (no dX, one plan for both directions) in the graph's own workspace region; the second sums the node

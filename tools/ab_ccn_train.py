@@ -26,7 +26,14 @@ profiles/ccn_train_optim_ab.json under the key "order<N>_<loss>_<optim>"; the fi
 same protocol -- the per-graph fused loop (order 2: fused2d) against, per B, the pieces route (fused=False) and the
 mini-batch kernels (order 1: fused=True, hgnn_ccn_small_train_batch, arm batch_fused_B<B>; order 2:
 fused="ccn2_batch", hgnn_ccn2_small_train_batch, arm batch_fused2d_B<B>); no torch arm.  Median, min and max ms per
-graph, merged into profiles/ccn_train_batch_ab.json under the key "order<N>_<loss>_<optim>"."""
+graph, merged into profiles/ccn_train_batch_ab.json under the key "order<N>_<loss>_<optim>".
+
+--spill: the spill instantiation of the CCN-1D kernels (CcnTrainStep(fused="ccn1_spill"): the row arrays in a global
+workspace) under the same protocol, two sections in one process, written to profiles/ccn_train_spill_ab.json:
+  replaces   256 three_collinear_points(n_max=50) graphs, CCN_1D(5, 2, 2, 8), classification -- shapes the LDS kernels
+             refuse: the spill loop against fused=False, and spill mini-batches at B = 32 and 256 against the pieces;
+  lds_price  the 256 QM9-shape graphs, CCN_1D(5, 1, 2, 2), MSE -- shapes both take: the spill loop and spill
+             mini-batches at B = 32 against the LDS kernels."""
 import argparse
 import copy
 import json
@@ -83,6 +90,74 @@ def batch_arms(args, net, inputs, stats, optim, nmax):
         f.write("\n")
 
 
+def _pad(graphs):
+    nmax = max(x.shape[0] for x, _, _ in graphs)
+    X = torch.zeros(len(graphs), nmax, graphs[0][0].shape[1])
+    A = torch.zeros(len(graphs), nmax, nmax)
+    for b, (x, a, _) in enumerate(graphs):
+        n = x.shape[0]
+        X[b, :n] = x
+        A[b, :n, :n] = a + torch.eye(n)
+    nb = torch.tensor([x.shape[0] for x, _, _ in graphs], dtype=torch.int64)
+    Y = torch.stack([t[0] for _, _, t in graphs]).view(-1, 1)
+    return (X.cuda(), A.cuda(), nb.cuda(), Y.cuda()), nmax
+
+
+def _alternate(arms, inputs):
+    """2 warm-up and 10 timed epochs per arm, arms alternating: {arm: min / median / max ms per graph}, paths."""
+    G = inputs[0].shape[0]
+    times = {k: [] for k in arms}
+    for it in range(12):
+        for k, st in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st.step(*inputs)
+            torch.cuda.synchronize()
+            if it >= 2:
+                times[k].append((time.perf_counter() - t0) * 1e3 / G)
+    res = {f"{k}_ms_per_graph": {"min": round(min(v), 5), "median": round(statistics.median(v), 5),
+                                 "max": round(max(v), 5)} for k, v in times.items()}
+    res.update(paths={k: st.path for k, st in arms.items()}, graphs=G, epochs=10)
+    return res
+
+
+def spill_arms():
+    """--spill: see the module docstring."""
+    import hgnn_amd.datagen as dg
+    from hgnn_amd.train import CcnTrainStep
+    from models.compnets.model_ccn import CCN_1D
+    out = {}
+    # the routes it replaces, on shapes the LDS kernels refuse
+    graphs = [(d[0], d[1], d[2].float()) for d in dg.three_collinear_points(256, n_max=50, seed=0)]
+    inputs, nmax = _pad(graphs)
+    torch.manual_seed(0)
+    net = CCN_1D(5, 2, 2, 8).cuda()
+    kw = dict(lr=LR, classification=True)
+    arms = {"loop_unfused": CcnTrainStep(copy.deepcopy(net), fused=False, **kw),
+            "loop_spill": CcnTrainStep(copy.deepcopy(net), fused="ccn1_spill", **kw)}
+    for B in (32, 256):
+        arms[f"batch_pieces_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused=False, batch_size=B, **kw)
+        arms[f"batch_spill_B{B}"] = CcnTrainStep(copy.deepcopy(net), fused="ccn1_spill", batch_size=B, **kw)
+    out["replaces"] = dict(_alternate(arms, inputs), model=[5, 2, 2, 8], loss="xent", nmax=nmax,
+                           data="three_collinear_points(256, n_max=50, seed=0)")
+    # the price of global rows, on shapes the LDS kernels take
+    inputs, nmax = _pad(dg.qm9_shape_dataset(256, seed=7))
+    torch.manual_seed(0)
+    net = CCN_1D(5, 1, 2, 2).cuda()
+    kw = dict(lr=LR, t_mean=MEAN, t_std=STD)
+    arms = {"loop_lds": CcnTrainStep(copy.deepcopy(net), fused=True, **kw),
+            "loop_spill": CcnTrainStep(copy.deepcopy(net), fused="ccn1_spill", **kw),
+            "batch_lds_B32": CcnTrainStep(copy.deepcopy(net), fused=True, batch_size=32, **kw),
+            "batch_spill_B32": CcnTrainStep(copy.deepcopy(net), fused="ccn1_spill", batch_size=32, **kw)}
+    out["lds_price"] = dict(_alternate(arms, inputs), model=[5, 1, 2, 2], loss="mse", nmax=nmax,
+                            data="qm9_shape_dataset(256, seed=7)")
+    print(json.dumps(out))
+    os.makedirs(os.path.join(REPO, "profiles"), exist_ok=True)
+    with open(os.path.join(REPO, "profiles", "ccn_train_spill_ab.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 def main():
     import hgnn_amd.datagen as dg
     from hgnn_amd.train import CcnTrainStep
@@ -93,7 +168,10 @@ def main():
     ap.add_argument("--optim", choices=("sgd", "adam", "adamax"), default=None)
     ap.add_argument("--momentum", type=float, default=0.9)
     ap.add_argument("--batch", type=int, nargs="+", default=None, metavar="B")
+    ap.add_argument("--spill", action="store_true")
     args = ap.parse_args()
+    if args.spill:
+        return spill_arms()
     xent, two = args.loss == "xent", args.order == 2
     if xent and two:
         graphs = [(x, a, torch.tensor([float(g % 2)]))
