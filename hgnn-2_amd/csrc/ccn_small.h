@@ -1,10 +1,21 @@
-// Device helpers of the CCN-1D small-graph kernels, shared by ccn_small.hip (the one-shot forward and backward and
-// the per-graph training loop) and ccn_small_batch.hip (the mini-batch training step): the LDS layout, the staging
-// round, the plan, one level of the forward and of the backward walk, the readout sums and the fc row.  Two
-// translation units, so that the mini-batch kernels' extra callers leave the other kernels' inlining, and with it
-// their code, alone.  The kernels themselves are templates in ccn_small_kernels.h and ccn_small_batch_kernels.h; their
-// SPILL instantiations (ccn_small_spill.hip, ccn_small_batch_spill.hip) keep the row-sized arrays in global memory
-// and take this code as it is, bar the three places marked SPILL below.
+// Device and host helpers of the CCN-1D small-graph kernels, shared by ccn_small.hip (the one-shot forward and backward
+// and the per-graph training loop), ccn_small_batch.hip (the mini-batch training step) and their SPILL units:
+//   * the LDS layout (CsLds, cs_carve), the staging round (cs_stage) and the plan (cs_plan);
+//   * one level of the forward and of the backward walk: cs_collect, cs_update, cs_fwd_level, cs_bwd_level;
+//   * the stages the kernels are lists of, each defined once: cs_open, cs_report, cs_levels_keep, cs_readout_sums,
+//     cs_out_row, cs_dsum, cs_fc_grads, cs_backward, and the per-element pair of the reductions over graphs,
+//     cs_param_elem / cs_sum_elem.  A stage inlines its level functions ([[clang::always_inline]]): the kernels run at
+//     the register cap, and an outlined level would spill the wave's state around every call;
+//   * the host side: the bounds, CsArgs from a config (cs_args, cs_set_grads), the workspace head, the LDS figures and
+//     the launch of a kernel's CH = 2 or CH = CS_CF instantiation.
+// k_ccn1_small_train (ccn_small_kernels.h) is the exception: it carries written-out copies of every stage, kept because
+// as calls they change its instruction stream (scratch of its SPILL instantiations, and a measured 0.6 % of the
+// classification loop); a change to a stage here goes there too.
+// Every stage carries a bitwise contract (fused step == pieces, mini-batch == pieces, spill == LDS), which is why there
+// is one definition.  The units stay separate translation units, so that one kernel's callers leave the others'
+// inlining, and with it their code, alone.  The kernels themselves are templates in ccn_small_kernels.h and
+// ccn_small_batch_kernels.h; their SPILL instantiations (ccn_small_spill.hip, ccn_small_batch_spill.hip) keep the
+// row-sized arrays in global memory and take this code as it is, bar the three places marked SPILL below.
 #pragma once
 #include <cstdint>
 #include <type_traits>
@@ -12,7 +23,6 @@
 #include "kernels.h"
 
 namespace hgnn {
-namespace {
 
 constexpr int CS_NT = 512, CS_NW = CS_NT / 64;   // 8 waves (~4 nodes of a QM9 graph each; 256 VGPRs a lane)
 constexpr int CS_RT = 256;                         // threads of the fp64 readout sums (the general path's order)
@@ -25,6 +35,10 @@ constexpr int CS_WMAX = CS_LMAX * CS_PMAX;            // staged level weights an
 constexpr size_t CS_FIXED = 512 + 256 + 272 + 4096 + 4 * CS_NW * CS_PMAX + 4 * CS_NFMAX + 8 * CS_NW * CS_CF +
                             4 * CS_XMAX + 4 * CS_WMAX;
 constexpr size_t CS_LDS_MAX = 150 * 1024;  // dynamic LDS opt-in (the forward also has a static word)
+// the training kernels (the per-graph loop and the mini-batch pair)
+constexpr int CS_TMAX = 2 * CS_LMAX + 2;    // parameter tensors: level weights and biases, fc weight and bias
+constexpr int CS_TRAIN_GMAX = 4096;         // graphs per call
+constexpr int CS_OMAX = CS_NW * CS_PMAX;    // n_out bound: out / dout of the graph live in CsLds::red
 
 struct CsArgs {
     const float* adj;        // (bs, nmax, nmax) with self loops
@@ -48,6 +62,8 @@ struct CsArgs {
     float* dX;               // (bs, nmax, f), padding rows zeroed
     unsigned long long* prof;  // diagnostic phase stamps of graph 0 (HGNN_CCN_SMALL_PROF), or null
 };
+
+namespace {
 
 // phase stamp k of graph 0 (s_memtime core cycles), diagnostic builds of the timing only
 #define CS_STAMP(k)                                                          \
@@ -583,6 +599,223 @@ __device__ void cs_bwd_level(const CsArgs& a, const CsLds& s, int b, int l, int 
     __syncthreads();
 }
 
+// ---------------------------------------------------------------- the stages of a kernel
+// Graph b opened: its node count, the staging round and the plan (n, nbr, bits, deg, off1 in LDS); the lanes'
+// validation bits are OR-ed into `bad`.  ST: the one-shot forward's phase stamps.
+template <bool ST = false>
+__device__ __forceinline__ int cs_open(const CsArgs& a, int b, const CsLds& s, float* As, uint32_t& bad) {
+    const int n = cs_nodes(a, b, bad);
+    cs_stage(a, b, n, s, As);
+    if constexpr (ST) CS_STAMP(1);
+    bad |= cs_plan(n, s, As);
+    if constexpr (ST) CS_STAMP(2);
+    return n;
+}
+
+// the lanes' validation bits into the block's word
+__device__ __forceinline__ void cs_report(uint32_t bad, uint32_t& sbad) {
+    bad = wave_or(bad);
+    if ((threadIdx.x & 63) == 0 && bad) atomicOr(&sbad, bad);
+}
+
+// Forward walk with every level kept: level l's rows at s.F + l * rcap * h (levels of <= 2 input channels take the
+// CF = 2 form)
+template <int CF, bool SPILL>
+__device__ __forceinline__ void cs_levels_keep(const CsArgs& a, const CsLds& s, int n, int G, const float* Xg) {
+    const int f = a.f, h = a.h;
+    for (int l = 0; l < a.L; ++l) {
+        const int cin = l == 0 ? f : h;
+        const float* fin = l == 0 ? nullptr : s.F + (size_t)(l - 1) * a.rcap * h;
+        float* fout = s.F + (size_t)l * a.rcap * h;
+        const float* Wl = s.Ws + cs_woff(l, f, h);
+        if (cin <= 2) [[clang::always_inline]] cs_fwd_level<2, SPILL>(s, n, G, Xg, fin, cin, Wl, h, fout);
+        else [[clang::always_inline]] cs_fwd_level<CF, SPILL>(s, n, G, Xg, fin, cin, Wl, h, fout);
+        __syncthreads();
+    }
+}
+
+// The readout features of the kept levels into s.vec: level 0's sum_i d_i X[i] (utils_ccn.py:212-216 tiles X[i] d_i
+// times), then every level's column sums over the graph's `rows` rows
+template <int CF>
+__device__ __forceinline__ void cs_readout_sums(const CsArgs& a, const CsLds& s, int n, int rows, const float* Xg) {
+    const int f = a.f, h = a.h;
+    cs_colsum<CF>(s, n, f, 0, [&](int r, int c) { return (double)s.deg[r] * (double)Xg[r * f + c]; });
+    for (int l = 0; l < a.L; ++l) {
+        const float* fl = s.F + (size_t)l * a.rcap * h;
+        cs_colsum<CF>(s, rows, h, f + l * h, [&](int r, int c) { return (double)fl[r * h + c]; });
+    }
+}
+
+// out = fc(feat) in fp64 (k_ccn_readout's order) from the features in s.vec: out_row[o], and keep[o] when the kernel
+// goes on with the row (keep: LDS, read after the caller's next barrier)
+__device__ __forceinline__ void cs_out_row(const CsArgs& a, const CsLds& s, int nf, int n_out, float* out_row,
+                                           float* keep) {
+    for (int o = 0; o < n_out; ++o) {
+        const double v = cs_fc(a, s, o, nf);
+        if (threadIdx.x == 0) {
+            const float ov = (float)(v + (double)a.fcb[o]);
+            out_row[o] = ov;
+            if (keep) keep[o] = ov;
+        }
+    }
+}
+
+// dsum[k] = sum_o dout[o] fcw[o][k] (k_ccn_readout_bwd's order) into s.vec, dob being the graph's dout row.
+__device__ __forceinline__ void cs_dsum(const CsArgs& a, const CsLds& s, const float* dob, int nf) {
+    for (int k = threadIdx.x; k < nf; k += CS_NT) {
+        float t = 0.f;
+        for (int o = 0; o < a.n_out; ++o) t = fmaf(dob[o], a.fcw[o * nf + k], t);
+        s.vec[k] = t;
+    }
+}
+
+// The fc gradients of one graph, written directly; feat: the graph's readout features, its workspace row or s.vec
+// before cs_dsum takes it
+__device__ __forceinline__ void cs_fc_grads(const CsArgs& a, const float* dob, const float* feat, int nf) {
+    for (int w = threadIdx.x; w < a.n_out * nf + a.n_out; w += CS_NT) {
+        if (w < a.n_out * nf) a.gfcw[w] = (float)((double)dob[w / nf] * (double)feat[w % nf]);
+        else a.gfcb[w - a.n_out * nf] = (float)(double)dob[w - a.n_out * nf];
+    }
+}
+
+// Backward level walk on the plan and the kept levels, dsum in s.vec: the top level down, the two dF buffers swapped
+// after each (graph b's partials or gradients, and with DX its dX rows)
+template <int CF, int CH, bool DX, bool SPILL>
+__device__ __forceinline__ void cs_backward(const CsArgs& a, const CsLds& s, int b, int n, int G, const float* Xg) {
+    float* dFc = s.dF0;
+    float* dFn = s.dF1;
+    for (int l = a.L - 1; l >= 0; --l) {
+        if ((l == 0 ? a.f : a.h) <= 2)
+            [[clang::always_inline]] cs_bwd_level<2, CH, DX, SPILL>(a, s, b, l, n, G, Xg, dFc, dFn);
+        else [[clang::always_inline]] cs_bwd_level<CF, CH, DX, SPILL>(a, s, b, l, n, G, Xg, dFc, dFn);
+        float* t = dFc;
+        dFc = dFn;
+        dFn = t;
+    }
+}
+
+// ---------------------------------------------------------------- per-element pair of the sums over graphs
+// Flat parameter element e (the levels in Ws' order -- ppart's -- then fc weight and bias) -> tensor ti (the
+// parameter list's index) and offset q in it.  nw = cs_woff(L, f, h) level entries and nfc = n_out nf fc weights: the
+// caller's, which has them for its bound (and the training loop keeps them out of its per-graph loop).
+__device__ __forceinline__ void cs_param_elem(const CsArgs& a, int nw, int nfc, int e, int& ti, int& q) {
+    if (e < nw) {
+        int l = 0;
+        while (l + 1 < a.L && e >= cs_woff(l + 1, a.f, a.h)) ++l;
+        q = e - cs_woff(l, a.f, a.h);
+        const int hk = a.h * 2 * (l == 0 ? a.f : a.h);
+        ti = 2 * l + (q < hk ? 0 : 1);
+        q = q < hk ? q : q - hk;
+    } else {
+        ti = 2 * a.L + (e < nw + nfc ? 0 : 1);
+        q = e - nw - (e < nw + nfc ? 0 : nfc);
+    }
+}
+// tensor ti's gradient
+__device__ __forceinline__ float* cs_grad(const CsArgs& a, int ti) {
+    if (ti < 2 * a.L) return (ti & 1) ? a.gB[ti >> 1] : a.gW[ti >> 1];
+    return ti == 2 * a.L ? a.gfcw : a.gfcb;
+}
+
+// Flat element w summed over B graphs in fp64, lane-strided (k_ccn_readout_bwd's order for the fc entries, from
+// dout [B][n_out] and the readout features); the wave's sum
+__device__ __forceinline__ double cs_sum_elem(const CsArgs& a, const float* dout, int B, int w) {
+    const int lane = threadIdx.x & 63;
+    const int nf = a.f + a.L * a.h, ptot = cs_woff(a.L, a.f, a.h);
+    double s = 0.0;
+    if (w < ptot) {
+        for (int b = lane; b < B; b += 64) s += (double)a.ppart[(long long)b * ptot + w];
+    } else if (w < ptot + a.n_out * nf) {
+        const int o = (w - ptot) / nf, k = (w - ptot) % nf;
+        for (int b = lane; b < B; b += 64) s += (double)dout[b * a.n_out + o] * (double)a.feat[(long long)b * nf + k];
+    } else {
+        const int o = w - ptot - a.n_out * nf;
+        for (int b = lane; b < B; b += 64) s += (double)dout[b * a.n_out + o];
+    }
+    return wave_sum_d(s);
+}
+
+// ---------------------------------------------------------------- host
+// the advertised bounds; the SPILL kernels take every shape within them
+bool cs_spill_ok(const hgnn_ccn_config* c) {
+    return c && c->order == 1 && c->bs > 0 && c->nmax > 0 && c->nmax <= 64 && c->f_in > 0 && c->f_in <= CS_CF &&
+           c->hidden > 0 && c->hidden <= CS_CF && c->layers >= 1 && c->layers <= CS_LMAX && c->n_out > 0;
+}
+
+// the LDS kernels: also the backward's LDS figure
+bool cs_ok(const hgnn_ccn_config* c) {
+    return cs_spill_ok(c) && cs_lds_bytes(c->nmax * c->nmax, c->f_in, c->hidden, c->layers, true) <= CS_LDS_MAX;
+}
+
+// whether the training kernels take graphs of this model padded to cfg->nmax (bs is not looked at)
+template <bool SPILL>
+bool cs_train_ok(const hgnn_ccn_config* cfg) {
+    if (!cfg) return false;
+    hgnn_ccn_config one = *cfg;
+    one.bs = 1;
+    return (SPILL ? cs_spill_ok(&one) : cs_ok(&one)) && one.n_out <= CS_OMAX;
+}
+
+// readout width, level parameter entries, and all parameter entries (the grid of the sums over graphs)
+int cs_nf(const hgnn_ccn_config* c) { return c->f_in + c->layers * c->hidden; }
+size_t cs_ptot(const hgnn_ccn_config* c) {
+    const int h = c->hidden, f = c->f_in;
+    return (size_t)(h * 2 * f + h) + (size_t)(c->layers - 1) * (h * 2 * h + h);
+}
+int cs_nouts(const hgnn_ccn_config* c) { return (int)cs_ptot(c) + c->n_out * cs_nf(c) + c->n_out; }
+
+// bytes of the one-shot calls' feat / ppart part of the workspace
+size_t cs_head_bytes(const hgnn_ccn_config* c) {
+    return (4 * (size_t)c->bs * cs_nf(c) + 255) / 256 * 256 + (c->bs > 1 ? 4 * (size_t)c->bs * cs_ptot(c) : 0);
+}
+
+// SPILL: the workspace starts with the row regions (region b at b * rstride floats; `regions` of them), then the
+// feat / ppart part as the LDS kernels lay it out
+template <bool SPILL = false>
+CsArgsT<SPILL> cs_args(const hgnn_ccn_config* c, const float* X, const float* adj, const int64_t* nb,
+                       const float* const* params, void* ws, int regions = 0) {
+    CsArgsT<SPILL> a{};
+    a.adj = adj;
+    a.n_batch = nb;
+    a.X = X;
+    a.bs = c->bs;
+    a.nmax = c->nmax;
+    a.f = c->f_in;
+    a.h = c->hidden;
+    a.L = c->layers;
+    a.n_out = c->n_out;
+    a.rcap = c->nmax * c->nmax;
+    for (int l = 0; l < c->layers; ++l) {
+        a.W[l] = params[2 * l];
+        a.B[l] = params[2 * l + 1];
+    }
+    a.fcw = params[2 * c->layers];
+    a.fcb = params[2 * c->layers + 1];
+    if constexpr (SPILL) {
+        a.rows = static_cast<float*>(ws);
+        a.rstride = (long long)cs_spill_stride(a.rcap, a.f, a.h, a.L);
+        ws = ws ? static_cast<char*>(ws) + 4 * (size_t)regions * a.rstride : nullptr;
+    }
+    a.feat = static_cast<float*>(ws);
+    if (ws) a.ppart = reinterpret_cast<float*>(static_cast<char*>(ws) + (4 * (size_t)c->bs * cs_nf(c) + 255) / 256 * 256);
+    return a;
+}
+
+void cs_set_grads(CsArgs& a, float* const* grads) {
+    for (int l = 0; l < a.L; ++l) {
+        a.gW[l] = grads[2 * l];
+        a.gB[l] = grads[2 * l + 1];
+    }
+    a.gfcw = grads[2 * a.L];
+    a.gfcb = grads[2 * a.L + 1];
+}
+
+// dynamic LDS of a launch; SPILL: at most 37.2 KB at nmax = 64, within the static limit (no opt-in)
+template <bool SPILL>
+size_t cs_lds_for(const CsArgs& a, bool bwd) {
+    return SPILL ? cs_spill_lds_bytes(a.rcap) : cs_lds_bytes(a.rcap, a.f, a.h, a.L, bwd);
+}
+
 // dynamic LDS opt-in of a kernel, once per instantiation (`done` is the caller's static flag)
 template <typename K>
 void cs_lds_attr(K kernel, bool& done) {
@@ -591,6 +824,19 @@ void cs_lds_attr(K kernel, bool& done) {
                                   (int)CS_LDS_MAX);
         (void)hipGetLastError();  // a refused opt-in shows at the launch, not here
         done = true;
+    }
+}
+
+// Launch of a kernel that exists as K2 (CH = 2, hidden <= 2) and K8 (CH = CS_CF), with the pick's LDS opt-in
+template <auto K2, auto K8, bool SPILL, typename... Args>
+void cs_launch_ch(int hidden, int blocks, size_t lds, hipStream_t s, const Args&... args) {
+    static bool attr2 = SPILL, attr8 = SPILL;
+    if (hidden <= 2) {
+        cs_lds_attr(K2, attr2);
+        HGNN_KLAUNCH(K2, dim3(blocks), dim3(CS_NT), lds, s, args...);
+    } else {
+        cs_lds_attr(K8, attr8);
+        HGNN_KLAUNCH(K8, dim3(blocks), dim3(CS_NT), lds, s, args...);
     }
 }
 

@@ -17,14 +17,36 @@
 // the same order, so forward values and input gradients are those of the general path; the weight
 // gradients are summed per lane over a wave's nodes, then over lanes and waves (fp32), where the general
 // path sums per node and then over nodes in fp64.
-// The device functions (cs_*) are in ccn_small.h, which ccn_small_batch.hip (the mini-batch training step) shares; the
-// kernels are the SPILL = false instantiations of ccn_small_kernels.h (ccn_small_spill.hip has the other form: the
-// row-sized arrays in a global workspace, for graphs the LDS layout does not hold).
-#include <cstdio>
-
+// The stages (cs_*) are in ccn_small.h, which ccn_small_batch.hip (the mini-batch training step) shares; the kernels
+// are the SPILL = false instantiations of ccn_small_kernels.h (ccn_small_spill.hip has the other form: the row-sized
+// arrays in a global workspace, for graphs the LDS layout does not hold).  k_ccn1_small_reduce lives here, behind
+// cs_launch_reduce, for both forms.
 #include "ccn_small_kernels.h"
 
 using namespace hgnn;
+
+namespace {
+
+// Batches: parameter gradient = sum over graphs in fp64, one wave per entry (the level entries, then fc
+// weight and bias from dout and the readout features, k_ccn_readout_bwd's order).
+__global__ void __launch_bounds__(256) k_ccn1_small_reduce(CsArgs a) {
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nw = cs_woff(a.L, a.f, a.h), nfc = a.n_out * (a.f + a.L * a.h);
+    if (w >= nw + nfc + a.n_out) return;
+    const double s = cs_sum_elem(a, a.dout, a.bs, w);
+    if ((threadIdx.x & 63) != 0) return;
+    int ti, q;
+    cs_param_elem(a, nw, nfc, w, ti, q);
+    cs_grad(a, ti)[q] = (float)s;
+}
+
+}  // namespace
+
+int hgnn::cs_launch_reduce(const hgnn_ccn_config* cfg, const CsArgs& a, hipStream_t s) {
+    HGNN_KLAUNCH(k_ccn1_small_reduce, dim3((cs_nouts(cfg) + 3) / 4), dim3(256), 0, s, a);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
 
 extern "C" {
 
@@ -64,32 +86,8 @@ int hgnn_ccn_small_forward(const hgnn_ccn_config* cfg, const float* d_X, const f
     if (two)
         return ccn2_small_forward(cfg, d_X, d_adj, d_n_batch, params, workspace, d_err, tag, d_out,
                                   (hipStream_t)stream);
-    CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, workspace);
-    a.out = d_out;
-    a.err = d_err;
-    a.tag = tag;
-    const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, false);
-    static bool attr = false;
-    cs_lds_attr(&k_ccn1_small_fwd<CS_CF>, attr);
-    const bool prof = switches().ccn_small_prof;
-    static unsigned long long* dprof = nullptr;
-    if (prof) {
-        if (!dprof) HGNN_HOST_CHECK(hipMalloc(&dprof, 32 * 8));
-        HGNN_HOST_CHECK(hipMemsetAsync(dprof, 0, 32 * 8, (hipStream_t)stream));
-        a.prof = dprof;
-    }
-    HGNN_KLAUNCH(k_ccn1_small_fwd<CS_CF>, dim3(cfg->bs), dim3(CS_NT), lds, (hipStream_t)stream, a);
-    HGNN_LAUNCH_CHECK();
-    if (prof) {  // diagnostic: phase cycles of graph 0 (synchronises)
-        unsigned long long hp[32];
-        HGNN_HOST_CHECK(hipMemcpyAsync(hp, dprof, sizeof(hp), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HGNN_HOST_CHECK(hipStreamSynchronize((hipStream_t)stream));
-        fprintf(stderr, "ccn_small_fwd cycles:");
-        for (int k = 1; k < 32; ++k)
-            if (hp[k]) fprintf(stderr, " %d:%llu", k, hp[k] - hp[0]);
-        fprintf(stderr, "\n");
-    }
-    return HGNN_OK;
+    return cs_forward_call<false>(cfg, d_X, d_adj, d_n_batch, params, workspace, d_err, tag, d_out,
+                                  (hipStream_t)stream);
 }
 
 int hgnn_ccn_small_backward(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
@@ -101,34 +99,8 @@ int hgnn_ccn_small_backward(const hgnn_ccn_config* cfg, const float* d_X, const 
     if (two)
         return ccn2_small_backward(cfg, d_X, d_adj, d_n_batch, params, workspace, d_dout, grads, d_dX,
                                    (hipStream_t)stream);
-    hipStream_t s = (hipStream_t)stream;
-    CsArgs a = cs_args(cfg, d_X, d_adj, d_n_batch, params, workspace);
-    a.dout = d_dout;
-    a.dX = d_dX;
-    for (int l = 0; l < cfg->layers; ++l) {
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gfcw = grads[2 * cfg->layers];
-    a.gfcb = grads[2 * cfg->layers + 1];
-    const size_t lds = cs_lds_bytes(a.rcap, a.f, a.h, a.L, true);
-    if (cfg->hidden <= 2) {
-        static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_bwd<CS_CF, 2>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_bwd<CS_CF, 2>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
-    } else {
-        static bool attr = false;
-        cs_lds_attr(&k_ccn1_small_bwd<CS_CF, CS_CF>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_bwd<CS_CF, CS_CF>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
-    }
-    HGNN_LAUNCH_CHECK();
-    if (cfg->bs > 1) {
-        const int nf = cfg->f_in + cfg->layers * cfg->hidden;
-        const int outs = (int)cs_ptot(cfg) + cfg->n_out * nf + cfg->n_out;
-        HGNN_KLAUNCH(k_ccn1_small_reduce, dim3((outs + 3) / 4), dim3(256), 0, s, a);
-        HGNN_LAUNCH_CHECK();
-    }
-    return HGNN_OK;
+    return cs_backward_call<false>(cfg, d_X, d_adj, d_n_batch, params, workspace, d_dout, grads, d_dX,
+                                   (hipStream_t)stream);
 }
 
 int hgnn_ccn_small_train_supported(const hgnn_ccn_config* cfg) {

@@ -1,8 +1,8 @@
 // CCN-1D mini-batch training past the LDS bound: the SPILL instantiation of k_ccn1_small_batch
 // (ccn_small_batch_kernels.h).  Workgroup b of a mini-batch keeps its row arrays in region b of the spill workspace
 // (ccn_small_spill.hip says what a region is and why that is coherent); the regions are reused mini-batch after
-// mini-batch, ordered by the stream like the rest of the workspace.  k_ccn1_small_apply and the workspace of
-// hgnn_ccn_small_train_batch are used as they are.
+// mini-batch, ordered by the stream like the rest of the workspace.  The workspace of hgnn_ccn_small_train_batch is used
+// as it is, and the apply kernel is ccn_small_batch.hip's (cb_launch_apply).
 #include "ccn_small_batch_kernels.h"
 
 using namespace hgnn;
@@ -19,7 +19,7 @@ int hgnn_ccn_small_spill_train_batch(const hgnn_ccn_config* cfg, int batch, int 
     if (!hgnn_ccn_small_spill_train_supported(cfg)) return HGNN_ERR_UNSUPPORTED;
     if (!d_X || !d_adj || !d_y || !params || !grads || !state1 || !d_steps || !d_stats || !d_out || !workspace ||
         !spill_workspace || !d_err || tag <= 0 || tag >= (1 << 23) || batch < 1 || cfg->bs < 1 ||
-        cfg->bs > CB_GMAX || (xent && cfg->n_out < 2))
+        cfg->bs > CS_TRAIN_GMAX || (xent && cfg->n_out < 2))
         return HGNN_ERR_ARG;
     // hgnn_ccn_small_train_batch's rule for the MSE meters' divisor
     if (!xent && (float)(t_std + 1e-8) < 1e-5f) return HGNN_ERR_ARG;

@@ -1,11 +1,18 @@
-// The CCN-1D small-graph kernels that own the carve (one-shot forward and backward, the per-graph training loop)
-// and their launch helpers, as templates on SPILL: ccn_small.hip instantiates the LDS form, ccn_small_spill.hip the
-// form whose row arrays live in a global region (ccn_small.h CsSpillArgs).  Two translation units, so that neither
-// form's callers touch the other's inlining.
+// The CCN-1D small-graph kernels that own the carve (one-shot forward and backward as lists of ccn_small.h's stages, the
+// per-graph training loop with its stages written out) and their host calls, as templates on SPILL: ccn_small.hip instantiates the LDS form,
+// ccn_small_spill.hip the form whose row arrays live in a global region (ccn_small.h CsSpillArgs).  Two translation
+// units, so that neither form's callers touch the other's inlining.  k_ccn1_small_reduce does not touch the row arrays:
+// it is compiled once, in ccn_small.hip, behind cs_launch_reduce.
 #pragma once
+#include <cstdio>
+
 #include "ccn_small.h"
 
 namespace hgnn {
+
+// The batch backward's sum of the per-graph partials into the gradients (ccn_small.hip)
+int cs_launch_reduce(const hgnn_ccn_config* cfg, const CsArgs& a, hipStream_t s);
+
 namespace {
 
 template <int CF, bool SPILL = false>
@@ -13,17 +20,12 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgsT<SPILL> a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ uint32_t sbad;
     const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63;
     const CsLds s = cs_carve<SPILL>(lds, a, false);
     float* As = cs_adj<SPILL>(lds, s);
     CS_STAMP(0);
     if (threadIdx.x == 0) sbad = 0;
     uint32_t bad = 0;
-    const int n = cs_nodes(a, b, bad);
-    cs_stage(a, b, n, s, As);
-    CS_STAMP(1);
-    bad |= cs_plan(n, s, As);
-    CS_STAMP(2);
+    const int n = cs_open<true>(a, b, s, As, bad);
     const float* Xg = s.Xs;
     const int h = a.h, f = a.f, nf = f + a.L * h;
     const int G = s.off1[66];
@@ -32,6 +34,8 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgsT<SPILL> a) {
     CS_STAMP(3);
     const int rows = s.off1[n];
     const float* fin = nullptr;
+    // its own level loop, not cs_levels_keep / cs_readout_sums: two ping-pong level buffers (the forward's LDS figure),
+    // each level's column sums between the levels, the phase stamps
     for (int l = 0; l < a.L; ++l) {
         const int cin = l == 0 ? f : h;
         float* fout = s.F + (size_t)(l & 1) * a.rcap * h;
@@ -45,14 +49,9 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_fwd(CsArgsT<SPILL> a) {
         fin = fout;
     }
     for (int k = threadIdx.x; k < nf; k += CS_NT) a.feat[(long long)b * nf + k] = s.vec[k];
-    // out = fc(feat) in fp64 (k_ccn_readout's order)
-    for (int o = 0; o < a.n_out; ++o) {
-        const double v = cs_fc(a, s, o, nf);
-        if (threadIdx.x == 0) a.out[(long long)b * a.n_out + o] = (float)(v + (double)a.fcb[o]);
-    }
+    cs_out_row(a, s, nf, a.n_out, a.out + (long long)b * a.n_out, nullptr);
     CS_STAMP(30);
-    bad = wave_or(bad);
-    if (lane == 0 && bad) atomicOr(&sbad, bad);
+    cs_report(bad, sbad);
     __syncthreads();
     if (threadIdx.x == 0 && sbad) a.err[0] = a.tag * 256 + (int)sbad;  // vector store (host-mapped word)
     CS_STAMP(31);
@@ -64,56 +63,25 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_bwd(CsArgsT<SPILL> a) {
     const int b = blockIdx.x;
     const CsLds s = cs_carve<SPILL>(lds, a, true);
     float* As = cs_adj<SPILL>(lds, s);
-    uint32_t bad = 0;
-    const int n = cs_nodes(a, b, bad);
-    cs_stage(a, b, n, s, As);
-    (void)cs_plan(n, s, As);  // the forward reported the batch's validation bits
+    uint32_t bad = 0;  // discarded: the forward reported the batch's validation bits
+    const int n = cs_open(a, b, s, As, bad);
     const float* Xg = s.Xs;
-    const int h = a.h, f = a.f, L = a.L, nf = f + L * h;
+    const int nf = a.f + a.L * a.h;
     const int G = s.off1[66];
-    // the levels again, all kept
-    for (int l = 0; l < L; ++l) {
-        const int cin = l == 0 ? f : h;
-        const float* fin = l == 0 ? nullptr : s.F + (size_t)(l - 1) * a.rcap * h;
-        float* fout = s.F + (size_t)l * a.rcap * h;
-        const float* Wl = s.Ws + cs_woff(l, f, h);
-        if (cin <= 2) cs_fwd_level<2, SPILL>(s, n, G, Xg, fin, cin, Wl, h, fout);
-        else cs_fwd_level<CF, SPILL>(s, n, G, Xg, fin, cin, Wl, h, fout);
-        __syncthreads();
-    }
-    // dsum[k] = sum_o dout[b][o] fcw[o][k] (k_ccn_readout_bwd's order); one graph: the fc gradients here
+    cs_levels_keep<CF, SPILL>(a, s, n, G, Xg);
+    // dsum; one graph: the fc gradients here (a batch's come from k_ccn1_small_reduce)
     const float* dob = a.dout + (long long)b * a.n_out;
-    for (int k = threadIdx.x; k < nf; k += CS_NT) {
-        float t = 0.f;
-        for (int o = 0; o < a.n_out; ++o) t = fmaf(dob[o], a.fcw[o * nf + k], t);
-        s.vec[k] = t;
-    }
-    if (a.bs == 1)
-        for (int w = threadIdx.x; w < a.n_out * nf + a.n_out; w += CS_NT) {
-            if (w < a.n_out * nf) a.gfcw[w] = (float)((double)dob[w / nf] * (double)a.feat[w % nf]);
-            else a.gfcb[w - a.n_out * nf] = (float)(double)dob[w - a.n_out * nf];
-        }
+    cs_dsum(a, s, dob, nf);
+    if (a.bs == 1) cs_fc_grads(a, dob, a.feat, nf);
     __syncthreads();
-    float* dFc = s.dF0;
-    float* dFn = s.dF1;
-    for (int l = L - 1; l >= 0; --l) {
-        if ((l == 0 ? f : h) <= 2) cs_bwd_level<2, CH, true, SPILL>(a, s, b, l, n, G, Xg, dFc, dFn);
-        else cs_bwd_level<CF, CH, true, SPILL>(a, s, b, l, n, G, Xg, dFc, dFn);
-        float* t = dFc;
-        dFc = dFn;
-        dFn = t;
-    }
-    for (int e = threadIdx.x; e < (a.nmax - n) * f; e += CS_NT) a.dX[((long long)b * a.nmax + n) * f + e] = 0.f;
+    cs_backward<CF, CH, true, SPILL>(a, s, b, n, G, Xg);
+    for (int e = threadIdx.x; e < (a.nmax - n) * a.f; e += CS_NT) a.dX[((long long)b * a.nmax + n) * a.f + e] = 0.f;
 }
 
 // The per-graph training loop of scripts/train_ccn.py:31-73 in one dispatch: one workgroup runs forward, loss,
 // backward and the Adamax step of graph 0, then of graph 1, ... (per-graph SGD is sequential: graph g + 1 reads
-// the weights graph g wrote).  The pieces are the forward's and the backward's (cs_* above, the one-graph form:
-// CsArgs::bs = 1), k_mse_loss's loss and meters and k_optim's element update (adamax_elem, sgd_elem or adam_elem).
-constexpr int CS_TMAX = 2 * CS_LMAX + 2;    // parameter tensors: level weights and biases, fc weight and bias
-constexpr int CS_TRAIN_GMAX = 4096;         // graphs per dispatch
-constexpr int CS_OMAX = CS_NW * CS_PMAX;    // n_out bound: out / dout of the graph live in CsLds::red
-
+// the weights graph g wrote).  The pieces are the forward's and the backward's (ccn_small.h's stages, the one-graph
+// form: CsArgs::bs = 1), k_mse_loss's loss and meters and k_optim's element update (adamax_elem, sgd_elem or adam_elem).
 struct CsTrain {
     const float* y;       // (G, n_out) raw targets
     const float* clr;     // the scalars of the dispatch's k-th applied step at clr[k * cstride] (and + 1: Adam's
@@ -158,7 +126,9 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgsT<SPILL> a, Cs
         run_m = t.stats[3];
     }
     for (int g = 0; g < t.G; ++g) {
-        // 1. stage (the current weights) and plan
+        // 1. stage (the current weights) and plan.  Stages 1, 2 and 5 are written out too (they mirror cs_open /
+        // cs_report, cs_levels_keep, cs_readout_sums, cs_out_row and cs_param_elem; a change there comes here): as calls
+        // they change this kernel's instruction stream, and the classification loop measured 0.6 % slower
         if (threadIdx.x == 0) sbad = 0;
         uint32_t bad = 0;
         const int n = cs_nodes(a, g, bad);
@@ -249,7 +219,9 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgsT<SPILL> a, Cs
                 t.stats[3] = run_m;
             }
         }
-        // 4. backward, k_ccn1_small_bwd's one-graph form: fc gradients from dout and feat, dsum, the levels
+        // 4. backward, k_ccn1_small_bwd's one-graph form: fc gradients from dout and feat, dsum, the levels.  Written
+        // out: cs_fc_grads, cs_dsum and cs_backward<CF, CH, false, SPILL> as calls cost the SPILL instantiations of
+        // CH = CS_CF 4 bytes of scratch per lane (profiles/ccn1_small_stages_resources.txt); a change there comes here
         const float* dob = s.red;
         for (int w = threadIdx.x; w < n_out * nf + n_out; w += CS_NT) {
             if (w < n_out * nf) a.gfcw[w] = (float)((double)dob[w / nf] * (double)s.vec[w % nf]);
@@ -308,100 +280,54 @@ __global__ void __launch_bounds__(CS_NT) k_ccn1_small_train(CsArgsT<SPILL> a, Cs
     }
 }
 
-// Batches: parameter gradient = sum over graphs in fp64, one wave per entry (the level entries, then fc
-// weight and bias from dout and the readout features, k_ccn_readout_bwd's order).
-__global__ void __launch_bounds__(256) k_ccn1_small_reduce(CsArgs a) {
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int h = a.h, f = a.f, L = a.L, nf = f + L * h;
-    const int p0 = h * 2 * f + h, p1 = h * 2 * h + h, ptot = p0 + (L - 1) * p1;
-    if (w >= ptot + a.n_out * nf + a.n_out) return;
-    double s = 0.0;
-    if (w < ptot) {
-        for (int b = lane; b < a.bs; b += 64) s += (double)a.ppart[(long long)b * ptot + w];
-    } else if (w < ptot + a.n_out * nf) {
-        const int o = (w - ptot) / nf, k = (w - ptot) % nf;
-        for (int b = lane; b < a.bs; b += 64) s += (double)a.dout[b * a.n_out + o] * (double)a.feat[(long long)b * nf + k];
-    } else {
-        const int o = w - ptot - a.n_out * nf;
-        for (int b = lane; b < a.bs; b += 64) s += (double)a.dout[b * a.n_out + o];
-    }
-    s = wave_sum_d(s);
-    if (lane != 0) return;
-    if (w < ptot) {
-        const int l = w < p0 ? 0 : 1 + (w - p0) / p1;
-        const int p = l == 0 ? w : (w - p0) % p1;
-        const int k2 = 2 * (l == 0 ? f : h);
-        if (p < h * k2) a.gW[l][p] = (float)s;
-        else a.gB[l][p - h * k2] = (float)s;
-    } else if (w < ptot + a.n_out * nf) {
-        a.gfcw[w - ptot] = (float)s;
-    } else {
-        a.gfcb[w - ptot - a.n_out * nf] = (float)s;
-    }
-}
-
-// the advertised bounds; the SPILL kernels take every shape within them
-bool cs_spill_ok(const hgnn_ccn_config* c) {
-    return c && c->order == 1 && c->bs > 0 && c->nmax > 0 && c->nmax <= 64 && c->f_in > 0 && c->f_in <= CS_CF &&
-           c->hidden > 0 && c->hidden <= CS_CF && c->layers >= 1 && c->layers <= CS_LMAX && c->n_out > 0;
-}
-
-// the LDS kernels: also the backward's LDS figure
-bool cs_ok(const hgnn_ccn_config* c) {
-    return cs_spill_ok(c) && cs_lds_bytes(c->nmax * c->nmax, c->f_in, c->hidden, c->layers, true) <= CS_LDS_MAX;
-}
-
-// whether the training kernels take graphs of this model padded to cfg->nmax (bs is not looked at)
+// The one-shot forward behind hgnn_ccn_small_forward / hgnn_ccn_small_spill_forward, their checks done.  SPILL: `ws`
+// starts with cfg->bs row regions.
 template <bool SPILL>
-bool cs_train_ok(const hgnn_ccn_config* cfg) {
-    if (!cfg) return false;
-    hgnn_ccn_config one = *cfg;
-    one.bs = 1;
-    return (SPILL ? cs_spill_ok(&one) : cs_ok(&one)) && one.n_out <= CS_OMAX;
-}
-
-size_t cs_ptot(const hgnn_ccn_config* c) {
-    const int h = c->hidden, f = c->f_in;
-    return (size_t)(h * 2 * f + h) + (size_t)(c->layers - 1) * (h * 2 * h + h);
-}
-
-// bytes of the one-shot calls' feat / ppart part of the workspace
-size_t cs_head_bytes(const hgnn_ccn_config* c) {
-    const int nf = c->f_in + c->layers * c->hidden;
-    return (4 * (size_t)c->bs * nf + 255) / 256 * 256 + (c->bs > 1 ? 4 * (size_t)c->bs * cs_ptot(c) : 0);
-}
-
-// SPILL: the workspace starts with the row regions (region b at b * rstride floats; `regions` of them), then the
-// feat / ppart part as the LDS kernels lay it out
-template <bool SPILL = false>
-CsArgsT<SPILL> cs_args(const hgnn_ccn_config* c, const float* X, const float* adj, const int64_t* nb,
-                       const float* const* params, void* ws, int regions = 0) {
-    CsArgsT<SPILL> a{};
-    a.adj = adj;
-    a.n_batch = nb;
-    a.X = X;
-    a.bs = c->bs;
-    a.nmax = c->nmax;
-    a.f = c->f_in;
-    a.h = c->hidden;
-    a.L = c->layers;
-    a.n_out = c->n_out;
-    a.rcap = c->nmax * c->nmax;
-    for (int l = 0; l < c->layers; ++l) {
-        a.W[l] = params[2 * l];
-        a.B[l] = params[2 * l + 1];
+int cs_forward_call(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
+                    const float* const* params, void* ws, int32_t* d_err, int32_t tag, float* d_out, hipStream_t s) {
+    CsArgsT<SPILL> a = cs_args<SPILL>(cfg, d_X, d_adj, d_n_batch, params, ws, cfg->bs);
+    a.out = d_out;
+    a.err = d_err;
+    a.tag = tag;
+    const size_t lds = cs_lds_for<SPILL>(a, false);
+    static bool attr = SPILL;
+    cs_lds_attr(&k_ccn1_small_fwd<CS_CF, SPILL>, attr);
+    if constexpr (!SPILL) {
+        if (switches().ccn_small_prof) {  // diagnostic: phase cycles of graph 0 (synchronises)
+            static unsigned long long* dprof = nullptr;
+            if (!dprof) HGNN_HOST_CHECK(hipMalloc(&dprof, 32 * 8));
+            HGNN_HOST_CHECK(hipMemsetAsync(dprof, 0, 32 * 8, s));
+            a.prof = dprof;
+            HGNN_KLAUNCH((k_ccn1_small_fwd<CS_CF, SPILL>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
+            HGNN_LAUNCH_CHECK();
+            unsigned long long hp[32];
+            HGNN_HOST_CHECK(hipMemcpyAsync(hp, dprof, sizeof(hp), hipMemcpyDeviceToHost, s));
+            HGNN_HOST_CHECK(hipStreamSynchronize(s));
+            fprintf(stderr, "ccn_small_fwd cycles:");
+            for (int k = 1; k < 32; ++k)
+                if (hp[k]) fprintf(stderr, " %d:%llu", k, hp[k] - hp[0]);
+            fprintf(stderr, "\n");
+            return HGNN_OK;
+        }
     }
-    a.fcw = params[2 * c->layers];
-    a.fcb = params[2 * c->layers + 1];
-    const int nf = c->f_in + c->layers * c->hidden;
-    if constexpr (SPILL) {
-        a.rows = static_cast<float*>(ws);
-        a.rstride = (long long)cs_spill_stride(a.rcap, a.f, a.h, a.L);
-        ws = ws ? static_cast<char*>(ws) + 4 * (size_t)regions * a.rstride : nullptr;
-    }
-    a.feat = static_cast<float*>(ws);
-    if (ws) a.ppart = reinterpret_cast<float*>(static_cast<char*>(ws) + (4 * (size_t)c->bs * nf + 255) / 256 * 256);
-    return a;
+    HGNN_KLAUNCH((k_ccn1_small_fwd<CS_CF, SPILL>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
+    HGNN_LAUNCH_CHECK();
+    return HGNN_OK;
+}
+
+// The one-shot backward behind hgnn_ccn_small_backward / hgnn_ccn_small_spill_backward
+template <bool SPILL>
+int cs_backward_call(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, const int64_t* d_n_batch,
+                     const float* const* params, void* ws, const float* d_dout, float* const* grads, float* d_dX,
+                     hipStream_t s) {
+    CsArgsT<SPILL> a = cs_args<SPILL>(cfg, d_X, d_adj, d_n_batch, params, ws, cfg->bs);
+    a.dout = d_dout;
+    a.dX = d_dX;
+    cs_set_grads(a, grads);
+    cs_launch_ch<&k_ccn1_small_bwd<CS_CF, 2, SPILL>, &k_ccn1_small_bwd<CS_CF, CS_CF, SPILL>, SPILL>(
+        cfg->hidden, cfg->bs, cs_lds_for<SPILL>(a, true), s, a);
+    HGNN_LAUNCH_CHECK();
+    return cfg->bs > 1 ? cs_launch_reduce(cfg, a, s) : HGNN_OK;
 }
 
 // Every training entry: the argument checks and the launch; XENT picks the loss stage (and ignores the target
@@ -429,12 +355,7 @@ int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, c
     a.out = d_out;
     a.err = d_err;
     a.tag = tag;
-    for (int l = 0; l < cfg->layers; ++l) {
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gfcw = grads[2 * cfg->layers];
-    a.gfcb = grads[2 * cfg->layers + 1];
+    cs_set_grads(a, grads);
     CsTrain t{};
     t.y = d_y;
     t.clr = d_clr;
@@ -450,18 +371,8 @@ int cs_train(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj, c
     }
     t.stats = d_stats;
     t.G = cfg->bs;
-    // SPILL: at most 37.2 KB at nmax = 64, within the static limit (no opt-in)
-    const size_t lds = SPILL ? cs_spill_lds_bytes(a.rcap) : cs_lds_bytes(a.rcap, a.f, a.h, a.L, true);
-    hipStream_t s = (hipStream_t)stream;
-    if (cfg->hidden <= 2) {
-        static bool attr = SPILL;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, 2, XENT, OPT, SPILL>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, 2, XENT, OPT, SPILL>), dim3(1), dim3(CS_NT), lds, s, a, t);
-    } else {
-        static bool attr = SPILL;
-        cs_lds_attr(&k_ccn1_small_train<CS_CF, CS_CF, XENT, OPT, SPILL>, attr);
-        HGNN_KLAUNCH((k_ccn1_small_train<CS_CF, CS_CF, XENT, OPT, SPILL>), dim3(1), dim3(CS_NT), lds, s, a, t);
-    }
+    cs_launch_ch<&k_ccn1_small_train<CS_CF, 2, XENT, OPT, SPILL>, &k_ccn1_small_train<CS_CF, CS_CF, XENT, OPT, SPILL>,
+                 SPILL>(cfg->hidden, 1, cs_lds_for<SPILL>(a, true), (hipStream_t)stream, a, t);
     HGNN_LAUNCH_CHECK();
     return HGNN_OK;
 }

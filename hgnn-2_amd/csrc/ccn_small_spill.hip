@@ -11,7 +11,7 @@
 //     the __syncthreads() the kernels have anyway; no new fence.  The training loop keeps its __threadfence() pair
 //     around the optimizer pass.
 //   * The staged adjacency, which aliases F in the LDS kernels, has nmax^2 floats of LDS of its own.
-// k_ccn1_small_reduce does not touch the row arrays and is the same kernel.
+// k_ccn1_small_reduce does not touch the row arrays: the batch backward launches ccn_small.hip's (cs_launch_reduce).
 #include "ccn_small_kernels.h"
 
 using namespace hgnn;
@@ -47,15 +47,8 @@ int hgnn_ccn_small_spill_forward(const hgnn_ccn_config* cfg, const float* d_X, c
     if (!cs_spill_ok(cfg)) return HGNN_ERR_UNSUPPORTED;
     if (!d_X || !d_adj || !params || !workspace || !d_err || !d_out || tag <= 0 || tag >= (1 << 23))
         return HGNN_ERR_ARG;
-    CsSpillArgs a = cs_args<true>(cfg, d_X, d_adj, d_n_batch, params, workspace, cfg->bs);
-    a.out = d_out;
-    a.err = d_err;
-    a.tag = tag;
-    // at most 37.2 KB at nmax = 64: within the static limit, no opt-in
-    HGNN_KLAUNCH((k_ccn1_small_fwd<CS_CF, true>), dim3(cfg->bs), dim3(CS_NT), cs_spill_lds_bytes(a.rcap),
-                 (hipStream_t)stream, a);
-    HGNN_LAUNCH_CHECK();
-    return HGNN_OK;
+    return cs_forward_call<true>(cfg, d_X, d_adj, d_n_batch, params, workspace, d_err, tag, d_out,
+                                 (hipStream_t)stream);
 }
 
 int hgnn_ccn_small_spill_backward(const hgnn_ccn_config* cfg, const float* d_X, const float* d_adj,
@@ -63,30 +56,8 @@ int hgnn_ccn_small_spill_backward(const hgnn_ccn_config* cfg, const float* d_X, 
                                   const float* d_dout, float* const* grads, float* d_dX, void* stream) {
     if (!cs_spill_ok(cfg)) return HGNN_ERR_UNSUPPORTED;
     if (!d_X || !d_adj || !params || !workspace || !d_dout || !grads || !d_dX) return HGNN_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    CsSpillArgs a = cs_args<true>(cfg, d_X, d_adj, d_n_batch, params, workspace, cfg->bs);
-    a.dout = d_dout;
-    a.dX = d_dX;
-    for (int l = 0; l < cfg->layers; ++l) {
-        a.gW[l] = grads[2 * l];
-        a.gB[l] = grads[2 * l + 1];
-    }
-    a.gfcw = grads[2 * cfg->layers];
-    a.gfcb = grads[2 * cfg->layers + 1];
-    const size_t lds = cs_spill_lds_bytes(a.rcap);
-    if (cfg->hidden <= 2)
-        HGNN_KLAUNCH((k_ccn1_small_bwd<CS_CF, 2, true>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
-    else
-        HGNN_KLAUNCH((k_ccn1_small_bwd<CS_CF, CS_CF, true>), dim3(cfg->bs), dim3(CS_NT), lds, s, a);
-    HGNN_LAUNCH_CHECK();
-    if (cfg->bs > 1) {
-        const int nf = cfg->f_in + cfg->layers * cfg->hidden;
-        const int outs = (int)cs_ptot(cfg) + cfg->n_out * nf + cfg->n_out;
-        const CsArgs& base = a;
-        HGNN_KLAUNCH(k_ccn1_small_reduce, dim3((outs + 3) / 4), dim3(256), 0, s, base);
-        HGNN_LAUNCH_CHECK();
-    }
-    return HGNN_OK;
+    return cs_backward_call<true>(cfg, d_X, d_adj, d_n_batch, params, workspace, d_dout, grads, d_dX,
+                                  (hipStream_t)stream);
 }
 
 int hgnn_ccn_small_spill_train(const hgnn_ccn_config* cfg, int kind, int xent, const float* d_X, const float* d_adj,

@@ -591,25 +591,23 @@ class CcnTrainStep(_Optimizer):
         padded to nmax nodes."""
         cfg = self.spec.config(1, nmax)
         name = "hgnn_ccn2_small_train_batch_supported" if two else "hgnn_ccn_small_train_batch_supported"
-        if not getattr(L.lib(), name)(ctypes.byref(cfg)):
-            return False
-        # a mini-batch is one call's at most; the entry's MSE meters are hgnn_mse_loss's, which stops dividing
-        # below (float)1e-5 where the CCN rule always divides (the entry's own fp32 comparison)
+        return bool(getattr(L.lib(), name)(ctypes.byref(cfg))) and self._batch_host_ok()
+
+    def _batch_host_ok(self):
+        """The mini-batch entries' two host-side conditions: a mini-batch is one call's at most; the entries' MSE
+        meters are hgnn_mse_loss's, which stops dividing below (float)1e-5 where the CCN rule always divides (the
+        entries' own fp32 comparison)."""
         f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]  # noqa: E731
         return self.batch_size <= CCN_TRAIN_MAX_GRAPHS and (self.classification
                                                             or f32(self.t_std + 1e-8) >= f32(1e-5))
 
     def _supported_spill(self, nmax):
         """Whether the spill kernels take chunks of this step padded to nmax nodes (mini-batch mode: with
-        _supported_batch's two host-side conditions)."""
+        _batch_host_ok)."""
         cfg = self.spec.config(1, nmax)
         if not L.lib().hgnn_ccn_small_spill_train_supported(ctypes.byref(cfg)):
             return False
-        if self.batch_size is None:
-            return True
-        f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]  # noqa: E731
-        return self.batch_size <= CCN_TRAIN_MAX_GRAPHS and (self.classification
-                                                            or f32(self.t_std + 1e-8) >= f32(1e-5))
+        return self.batch_size is None or self._batch_host_ok()
 
     def _route_spill(self, nmax):
         if not self._supported_spill(nmax):
